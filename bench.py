@@ -18,8 +18,17 @@ Other configs (--config): c1 Rosenbrock ProxLQNSCORE (configs[0]), c2 ProxNSCORE
 logistic N=100k m=8k (configs[1]), c4 ProxGGNSCORE sparse-group lasso N=4M m=32k
 (configs[3]; needs >= 4 GPUs at full size).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run does what the headline figure needs and no more: set up, warm up, time the K epochs,
+write the outputs if asked, print the JSON line (with the roofline and per-kernel figures that the
+timed call's own HIP events give for free).  --steps and --warmup are taken as given.
+--dump-outputs DIR writes the timed call's Solution (x, the histories) as DIR/<name>.npy; the
+problem comes from fixed seeds, so the same arguments give the same inputs on every run.
+--full adds the legs that take runs of their own: the sampled full-size parity check against host
+fp64 (parity_check; a failure exits non-zero) and the CPU baseline subprocess (cpu_baseline);
+--no-check / --no-cpu-baseline drop one of them.
 
 Multi-GPU: under torchrun / torch.distributed.run (WORLD_SIZE set) every process is
 one rank and WORLD_SIZE must equal --gpus.  Without WORLD_SIZE, --gpus N > 1 starts
@@ -164,6 +173,21 @@ def sparse_check(model, x, seed=7, f32_compute=False):
             "bound": "%g * sum|terms| per entry (host SciPy CSR, fp64)%s" % (
                 tol, "; fp32-arithmetic arm" if f32_compute else ""),
             "pass": bool(err_f <= 1.0 and err_g <= 1.0)}
+
+
+def dump_outputs(path, sol):
+    """--dump-outputs: what the timed iterate!() call returned (its Solution after the last epoch) as
+    float64 .npy files -- x and the per-push histories obj, fval, rel, objrel, pri_res_norm (without
+    its first entry, which is `nothing` before any step).  `times` (wall clock) is left out.  The
+    problem is generated from fixed seeds, so two builds given the same arguments can be compared
+    file by file.  Under 1 MB (m doubles + at most 2·steps + 1 entries per history)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    out = {"x": sol.x, "obj": sol.obj, "fval": sol.fval, "rel": sol.rel, "objrel": sol.objrel,
+           "pri_res_norm": [v for v in sol.pri_res_norm if v is not None]}
+    for name, v in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(v, dtype=np.float64))
+    return {"dir": path, "files": sorted(n + ".npy" for n in out)}
 
 
 def host_info():
@@ -382,8 +406,15 @@ def plumbing_check(world, rank, local, args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
-    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed epochs, exactly as given (default 3; 50 for the micro- / millisecond-scale c1 and c5)")
+    ap.add_argument("--warmup", type=int, default=None,
+                    help="warm-up epochs before the timed call, exactly as given (default 1; 5 for c5)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed run also do what the headline figure does not need: the sampled full-size "
+                         "parity check and the CPU baseline (a plain run sets up, warms up, times and prints)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the Solution of the timed iterate!() call (x and the histories) as DIR/<name>.npy")
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
     ap.add_argument("--N", type=int, default=0, help="override the config's N")
     ap.add_argument("--m", type=int, default=0, help="override the config's m")
@@ -394,8 +425,8 @@ def main():
     ap.add_argument("--gram-cache", action="store_true",
                     help="c4: reuse the x-independent AᵀQA of least squares across steps (scs_set_gram_cache; "
                          "reported separately -- the reference recomputes it every step)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-check", action="store_true", help="skip the sampled full-size Gram / Aᵀv check")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-check", action="store_true", help="--full without the sampled full-size Gram / Aᵀv check")
     ap.add_argument("--comm", default="rccl", choices=["rccl", "torch"],
                     help="row-shard exchange: libscsopt's own RCCL communicator or a torch.distributed callback")
     ap.add_argument("--force-comm", action="store_true",
@@ -415,6 +446,8 @@ def main():
                     help="launch the ranks and check their world wiring over gloo, no GPU work")
     args = ap.parse_args()
     cfg = CONFIGS[args.config]
+    if (args.steps is not None and args.steps < 1) or (args.warmup is not None and args.warmup < 0):
+        raise SystemExit(f"--steps must be >= 1 and --warmup >= 0 (got {args.steps}, {args.warmup})")
 
     world, rank, local, spawn = world_from_env(args, os.environ)
     single = args.single_process and args.gpus > 1
@@ -510,13 +543,15 @@ def main():
         # and the history bookkeeping.  x_tol = f_tol = 0 so every call runs exactly k epochs.
         return device_optim_loop(method, model, reg, hmu, max_epoch=k, x_tol=0.0, f_tol=0.0, verbose=0)
 
-    steps, warmup = args.steps, args.warmup
-    if cfg["loss"] == "rosenbrock" and steps < 50:
-        steps = 50                               # microsecond-scale steps: time a meaningful batch
+    # --steps / --warmup are taken as given; only their defaults depend on the config
     lqn_sparse = cfg.get("sparse") and cfg["method"] == "lqn"
-    if lqn_sparse:
-        steps = max(steps, 50)                   # millisecond-scale steps: amortize iterate!'s f(x*) once
-        warmup = max(warmup, 5)                  # and let the clocks settle (1 warm-up step: +-5 % box to box)
+    steps, warmup = args.steps, args.warmup
+    if steps is None:
+        # microsecond-scale (c1) / millisecond-scale (c5) steps: time a meaningful batch and amortize
+        # iterate!'s f(x*) once
+        steps = 50 if cfg["loss"] == "rosenbrock" or lqn_sparse else 3
+    if warmup is None:
+        warmup = 5 if lqn_sparse else 1          # c5: let the clocks settle (1 warm-up step: +-5 % box to box)
     # kernel timing: HIP events around the dominant launches inside the timed region.  Each event record
     # costs a dispatch gap (~5 us) of its own, so the millisecond-scale sparse epochs time the launches of
     # every TEVERY-th epoch (scs_iterate's pipelined loop; the setup passes are always timed)
@@ -548,10 +583,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
 
+    dumped = dump_outputs(args.dump_outputs, sol) if rank == 0 and args.dump_outputs else None
+
     check = None
-    if rank == 0 and not cfg.get("sparse") and cfg["loss"] != "rosenbrock" and not args.no_check and not single:
+    do_check = args.full and rank == 0 and not args.no_check
+    if do_check and not cfg.get("sparse") and cfg["loss"] != "rosenbrock" and not single:
         check = sampled_gram_check(model, m)   # kernel-level entry points: single-device contexts
-    if rank == 0 and cfg.get("sparse") and not args.no_check:
+    if do_check and cfg.get("sparse"):
         check = sparse_check(model, np.asarray(sol.x, dtype=np.float64), f32_compute=args.f32_compute)
 
     if rank == 0:
@@ -713,7 +751,10 @@ def main():
         line["objective_last"] = objs[-1]
         if check is not None:
             line["parity_check"] = check
-        do_cpu = not args.no_cpu_baseline and world == 1 and not single   # the CPU baseline: rank 0 at N = 1 only
+        if dumped is not None:
+            line["outputs"] = dumped
+        # the CPU baseline (--full): rank 0 at N = 1 only
+        do_cpu = args.full and not args.no_cpu_baseline and world == 1 and not single
         if do_cpu and args.config == "c1":
             try:
                 out = subprocess.run([sys.executable, os.path.join(ROOT, "oracle", "cpu_baseline_c1.py")],

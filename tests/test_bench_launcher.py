@@ -92,6 +92,29 @@ def test_world_mismatch_exits_nonzero():
     assert r.returncode != 0 and "WORLD_SIZE=2 but --gpus 4" in r.stderr
 
 
+def test_steps_are_taken_as_given():
+    """--steps 0 is refused (before anything touches a GPU), not raised to a default."""
+    r = _bench("--steps", "0")
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr
+
+
+def test_dump_outputs(tmp_path):
+    """--dump-outputs: the Solution's x and histories as float64 .npy files, pri_res_norm without its
+    leading `nothing`, the wall-clock `times` left out."""
+    import numpy as np
+    from types import SimpleNamespace
+    sol = SimpleNamespace(x=np.arange(5.0), obj=[3.0, 2.0, 2.0], fval=[2.5, 1.5, 1.5], rel=[1.0, 0.5, 0.5],
+                          objrel=[0.2, 0.1, 0.1], pri_res_norm=[None, 0.25, 0.25], times=[0.0, 0.1, 0.1])
+    d = tmp_path / "out"
+    rec = bench.dump_outputs(str(d), sol)
+    assert rec["files"] == sorted(p.name for p in d.iterdir())
+    assert rec["files"] == ["fval.npy", "obj.npy", "objrel.npy", "pri_res_norm.npy", "rel.npy", "x.npy"]
+    for name in ("x", "obj", "fval", "rel", "objrel"):
+        a = np.load(d / (name + ".npy"))
+        assert a.dtype == np.float64 and np.array_equal(a, np.asarray(getattr(sol, name)))
+    assert np.array_equal(np.load(d / "pri_res_norm.npy"), [0.25, 0.25])
+
+
 def test_verify_ranks():
     rows = [{"rank": r, "row0": a, "row1": b, "comm": {"kind": "rccl", "nranks": 4, "rank": r}}
             for r, (a, b) in enumerate([(0, 3), (3, 6), (6, 8), (8, 10)])]
