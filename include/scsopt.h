@@ -214,6 +214,32 @@ int scs_set_loss_callback(scs_ctx* ctx, scs_loss_fn fn, void* user, int64_t ggn_
 int scs_set_data(scs_ctx* ctx, int64_t N, int64_t m, const double* A, int64_t lda,
                  const double* y, int64_t N_global, int64_t row0);
 int scs_gen_data(scs_ctx* ctx, const scs_synth* spec);
+/* ---- fp32 storage of a dense A  (Problem(A::Matrix{Float32}, y, x0::Vector{Float64}, ...):
+ * A::DataTupleOrArray2 admits any Real element type, problems.jl:61-62, types/custom.jl:15, and
+ * Julia promotes every product with the Float64 x to Float64 -- fp32 values, fp64 arithmetic).
+ * on = 1: the dense row blocks uploaded or generated AFTER the call (scs_set_data, scs_gen_data,
+ * scs_set_test_data, scs_gen_test_data, and the minibatch views gathered from them) are stored as
+ * fp32 on the device, half the memory and half the bytes of every pass over A; fp64 input is
+ * rounded to nearest even while the panel-blocked block is written, and scs_gen_data forms y from
+ * the stored (rounded) rows.  Every kernel widens the stored values on load and runs the fp64
+ * kernel's arithmetic in its order, so an fp32-stored context produces, bit for bit, what an
+ * fp64-stored context produces from the same values widened to fp64 (products, Gram, Aᵀv, x,
+ * every history array).  Weights, y, z, the Gram, the factorizations and all m-vectors stay fp64;
+ * scs_set_compute_f32 is independent of this.  scs_get_data / scs_get_columns return the stored
+ * values widened.  The mode persists across scs_set_data (as scs_set_solver's choice does).  No
+ * effect on sparse data (its dense mirror and dense batches stay fp64).  Default 0.
+ * With fp32-stored data the main Gram runs the default interleaved kernel whatever SCS_GRAM_SIA /
+ * SCS_GRAM_GLDS select.  SCS_LOSS_QUADRATIC (an m x m operator A) is refused with SCS_ERR_ARG.  */
+int scs_set_dense_f32(scs_ctx* ctx, int on);
+/* Host fp32 rows (float, column-major, N x m, leading dim lda), stored as they are: the host never
+ * widens them.  Switches the mode on, as scs_set_dense_f32(ctx, 1) would.  A32 points to float
+ * (void*: bindings pass an untyped pointer); it must not be NULL.                             */
+int scs_set_data_f32(scs_ctx* ctx, int64_t N, int64_t m, const void* A32, int64_t lda,
+                     const double* y, int64_t N_global, int64_t row0);
+/* a_elem_bytes: element size of the dense A (8, or 4 when stored fp32); a_bytes: bytes of that block
+ * (0 without one); ctx_bytes: device bytes the context holds now, summed over its own allocations
+ * (a multi-device context: device 0's element size, bytes summed).  Any pointer may be NULL.    */
+int scs_data_info(scs_ctx* ctx, int* a_elem_bytes, int64_t* a_bytes, int64_t* ctx_bytes);
 /* ---- held-out data  (Problem(A, y, x0, f, λ; Atest, ytest), problems.jl:27-28,67-68) -------
  * optim_loop! evaluates ftest(x) = f(Atest, ytest, x) with the problem's own f (same loss kind,
  * same scale literal) at every stats push when BOTH Atest and ytest are given (iterate.jl:169-175,
@@ -226,6 +252,10 @@ int scs_gen_data(scs_ctx* ctx, const scs_synth* spec);
  * scs_iterate_ex then raises the reference's UndefVarError at its first stats push.             */
 int scs_set_test_data(scs_ctx* ctx, int64_t N, const double* A, int64_t lda, const double* y,
                       int64_t N_global, int64_t row0);
+/* The same with host fp32 rows (Atest::Matrix{Float32}), stored as they are; switches the fp32
+ * storage mode on (scs_set_dense_f32).  Dense held-out rows of an fp32-mode context are fp32.   */
+int scs_set_test_data_f32(scs_ctx* ctx, int64_t N, const void* A32, int64_t lda, const double* y,
+                          int64_t N_global, int64_t row0);
 /* CSR held-out rows (0-based, m columns; values stored fp64, or fp32 with val_f32 = 1).       */
 int scs_set_test_sparse(scs_ctx* ctx, int64_t N, int64_t nnz, const int64_t* rowptr, const int32_t* colidx,
                         const double* val, int val_f32, const double* y, int64_t N_global, int64_t row0);
@@ -432,7 +462,9 @@ int scs_timing_enable(scs_ctx* ctx, int on);
 int scs_timing_get(scs_ctx* ctx, scs_timing* out);
 int scs_timing_reset(scs_ctx* ctx);
 /* The kernels of the latest main Gram launch and sparse product launch, as rocprofv3 names them
- * ("" when none ran), NUL-terminated, truncated to the capacities.                          */
+ * ("" when none ran), NUL-terminated, truncated to the capacities.  On an fp32-stored dense A
+ * (scs_set_dense_f32) the Gram is gram_sia_ta_kernel<float, ...> and `product` names the A x
+ * kernel, gemv_n_kernel<float>.                                                              */
 int scs_kernel_names(scs_ctx* ctx, char* gram, int64_t gram_cap, char* product, int64_t product_cap);
 /* Fallbacks taken instead of failing (r06), counted since the context was created (a
  * multi-device context: summed over its devices).  counts[i] for i < n:

@@ -16,6 +16,18 @@ constexpr double JL_EPS = 2.220446049250313e-16;  // Julia eps()
 
 typedef double v2d __attribute__((ext_vector_type(2)));
 typedef double v4d __attribute__((ext_vector_type(4)));
+typedef float v2f __attribute__((ext_vector_type(2)));
+
+// two consecutive elements of the panel-blocked A as fp64: an fp32-stored A (scs_set_dense_f32) is
+// widened on load, exactly, so everything downstream of the load is the fp64 kernel's
+__device__ __forceinline__ v2d ld_pair(const double* p) { return *(const v2d*)p; }
+__device__ __forceinline__ v2d ld_pair(const float* p) { return __builtin_convertvector(*(const v2f*)p, v2d); }
+// the same in two steps, for kernels that keep the pair in registers as loaded (gram_sia_body.h)
+template <typename T> struct pair_of;
+template <> struct pair_of<double> { typedef v2d type; };
+template <> struct pair_of<float> { typedef v2f type; };
+__device__ __forceinline__ v2d widen(v2d v) { return v; }
+__device__ __forceinline__ v2d widen(v2f v) { return __builtin_convertvector(v, v2d); }
 
 // ---- Julia scalar semantics ------------------------
 // Base._isless(x, y) = (x < y) || (signbit(x) > signbit(y))

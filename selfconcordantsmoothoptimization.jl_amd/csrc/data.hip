@@ -34,7 +34,10 @@ int gemv_n_splits(int64_t Npad, int64_t m) {
 // thread = 2 consecutive samples (one v2d of a block row); a wave covers 8
 // stages, so each load instruction reads 8 full 128-B lines.  Columns [c0, c1)
 // are whole panels; x must be zero beyond m (callers pass m_pad-sized x).
-__global__ __launch_bounds__(256) void gemv_n_kernel(const double* __restrict__ A, int64_t S, int64_t Npad,
+// TA (here and below): the stored element type of A, double or float (scs_set_dense_f32); a float
+// A is widened in the load (ld_pair), the arithmetic and its order are the fp64 kernel's.
+template <typename TA>
+__global__ __launch_bounds__(256) void gemv_n_kernel(const TA* __restrict__ A, int64_t S, int64_t Npad,
                                                      int64_t mpad, const double* __restrict__ x, int64_t cps,
                                                      double* __restrict__ part, int64_t ldo) {
   const int64_t r = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 2;
@@ -43,18 +46,18 @@ __global__ __launch_bounds__(256) void gemv_n_kernel(const double* __restrict__ 
   const int64_t c1 = (c0 + cps < mpad) ? c0 + cps : mpad;
   v2d acc0 = {0.0, 0.0}, acc1 = {0.0, 0.0};
   for (int64_t pc = c0; pc < c1; pc += 128) {
-    const double* p = A + tiled_off(S, r, pc);
+    const TA* p = A + tiled_off(S, r, pc);
     const double* xp = x + pc;
 #pragma unroll 4
     for (int f = 0; f < 128; f += 8) {
-      const v2d a0 = *(const v2d*)(p + 16 * (f + 0));
-      const v2d a1 = *(const v2d*)(p + 16 * (f + 1));
-      const v2d a2 = *(const v2d*)(p + 16 * (f + 2));
-      const v2d a3 = *(const v2d*)(p + 16 * (f + 3));
-      const v2d a4 = *(const v2d*)(p + 16 * (f + 4));
-      const v2d a5 = *(const v2d*)(p + 16 * (f + 5));
-      const v2d a6 = *(const v2d*)(p + 16 * (f + 6));
-      const v2d a7 = *(const v2d*)(p + 16 * (f + 7));
+      const v2d a0 = ld_pair(p + 16 * (f + 0));
+      const v2d a1 = ld_pair(p + 16 * (f + 1));
+      const v2d a2 = ld_pair(p + 16 * (f + 2));
+      const v2d a3 = ld_pair(p + 16 * (f + 3));
+      const v2d a4 = ld_pair(p + 16 * (f + 4));
+      const v2d a5 = ld_pair(p + 16 * (f + 5));
+      const v2d a6 = ld_pair(p + 16 * (f + 6));
+      const v2d a7 = ld_pair(p + 16 * (f + 7));
       acc0 += a0 * xp[f];
       acc1 += a1 * xp[f + 1];
       acc0 += a2 * xp[f + 2];
@@ -68,7 +71,7 @@ __global__ __launch_bounds__(256) void gemv_n_kernel(const double* __restrict__ 
   *(v2d*)(part + (int64_t)blockIdx.y * ldo + r) = acc0 + acc1;
 }
 
-hipError_t launch_gemv_n(const double* A, int64_t S, int64_t Npad, int64_t mpad, const double* x, int nsplit,
+hipError_t launch_gemv_n(const void* A, int a32, int64_t S, int64_t Npad, int64_t mpad, const double* x, int nsplit,
                          double* part, int64_t ldo, hipStream_t st) {
   const int64_t np = mpad / 128;
   const int64_t pps = ceil_div(np, nsplit);   // panels per split
@@ -78,8 +81,13 @@ hipError_t launch_gemv_n(const double* A, int64_t S, int64_t Npad, int64_t mpad,
     hipError_t e = hipMemsetAsync(part + (int64_t)ns * ldo, 0, sizeof(double) * ldo * (nsplit - ns), st);
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL(gemv_n_kernel, dim3((unsigned)ceil_div(Npad, GN_ROWS), (unsigned)ns), dim3(256), 0, st, A, S,
-                     Npad, mpad, x, pps * 128, part, ldo);
+  const dim3 grid((unsigned)ceil_div(Npad, GN_ROWS), (unsigned)ns);
+  if (a32)
+    hipLaunchKernelGGL(gemv_n_kernel<float>, grid, dim3(256), 0, st, (const float*)A, S, Npad, mpad, x, pps * 128, part,
+                       ldo);
+  else
+    hipLaunchKernelGGL(gemv_n_kernel<double>, grid, dim3(256), 0, st, (const double*)A, S, Npad, mpad, x, pps * 128,
+                       part, ldo);
   return hipGetLastError();
 }
 
@@ -188,7 +196,8 @@ __global__ __launch_bounds__(1024) void sum_partials_kernel(const double* __rest
 }
 
 // At (n-major: At[n*ldt + f] = A[f*lda + n]) for the sample-space Gram A diag(h) Aᵀ; zero padded
-__global__ void transpose_kernel(const double* __restrict__ A, int64_t Npad, int64_t N, int64_t m,
+template <typename TA>
+__global__ void transpose_kernel(const TA* __restrict__ A, int64_t Npad, int64_t N, int64_t m,
                                  double* __restrict__ At, int64_t ldt, int64_t nt) {
   const int64_t S = Npad / 16;
   __shared__ double tile[32][33];
@@ -196,7 +205,7 @@ __global__ void transpose_kernel(const double* __restrict__ A, int64_t Npad, int
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 32 x 8
   for (int j = ty; j < 32; j += 8) {
     const int64_t f = f0 + j, n = n0 + tx;
-    tile[j][tx] = (f < m && n < N) ? A[tiled_off(S, n, f)] : 0.0;
+    tile[j][tx] = (f < m && n < N) ? (double)A[tiled_off(S, n, f)] : 0.0;
   }
   __syncthreads();
   for (int j = ty; j < 32; j += 8) {
@@ -205,19 +214,24 @@ __global__ void transpose_kernel(const double* __restrict__ A, int64_t Npad, int
   }
 }
 
-hipError_t launch_transpose(const double* A, int64_t Npad, int64_t N, int64_t m, double* At, int64_t ldt,
+hipError_t launch_transpose(const void* A, int a32, int64_t Npad, int64_t N, int64_t m, double* At, int64_t ldt,
                             int64_t nt, hipStream_t st) {
-  hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)ceil_div(ldt, 32), (unsigned)ceil_div(nt, 32)), dim3(256), 0,
-                     st, A, Npad, N, m, At, ldt, nt);
+  const dim3 grid((unsigned)ceil_div(ldt, 32), (unsigned)ceil_div(nt, 32));
+  if (a32)
+    hipLaunchKernelGGL(transpose_kernel<float>, grid, dim3(256), 0, st, (const float*)A, Npad, N, m, At, ldt, nt);
+  else
+    hipLaunchKernelGGL(transpose_kernel<double>, grid, dim3(256), 0, st, (const double*)A, Npad, N, m, At, ldt, nt);
   return hipGetLastError();
 }
 
 // Minibatch gather (iterate.jl:141-145, 205-207: the DataLoader batch As, ys of a step!):
 // rows[0..n) of the panel-blocked A (Npad rows) -> a panel-blocked batch Ab (Npad_b rows,
 // zero padding), y -> yb.  Threads walk the OUTPUT layout, so the writes are coalesced.
-__global__ void gather_rows_kernel(const double* __restrict__ A, int64_t Npad, const double* __restrict__ y,
+// TD: the batch's element type (TA, or double from a float A: the sharded sample-space gather).
+template <typename TA, typename TD>
+__global__ void gather_rows_kernel(const TA* __restrict__ A, int64_t Npad, const double* __restrict__ y,
                                    const int64_t* __restrict__ rows, int64_t n, int64_t Npad_b, int64_t mpad,
-                                   double* __restrict__ Ab, double* __restrict__ yb) {
+                                   TD* __restrict__ Ab, double* __restrict__ yb) {
   const int64_t S = Npad / 16, Sb = Npad_b / 16;
   const int64_t total = Npad_b * mpad;
   for (int64_t o = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; o < total; o += (int64_t)gridDim.x * blockDim.x) {
@@ -225,35 +239,56 @@ __global__ void gather_rows_kernel(const double* __restrict__ A, int64_t Npad, c
     const int64_t s = ps % Sb, p = ps / Sb;
     const int64_t r = s * 16 + t, j = p * 128 + f;
     const int64_t src = (r < n) ? rows[r] : -1;   // -1: a zero row (rows held by other ranks)
-    Ab[o] = (src >= 0) ? A[tiled_off(S, src, j)] : 0.0;
+    Ab[o] = (src >= 0) ? (TD)A[tiled_off(S, src, j)] : (TD)0;
     if (j == 0) yb[r] = (src >= 0) ? y[src] : 0.0;
   }
 }
 
-hipError_t launch_gather_rows(const double* A, int64_t Npad, const double* y, const int64_t* rows, int64_t n,
-                              int64_t Npad_b, int64_t mpad, double* Ab, double* yb, hipStream_t st) {
+hipError_t launch_gather_rows(const void* A, int a32, int64_t Npad, const double* y, const int64_t* rows, int64_t n,
+                              int64_t Npad_b, int64_t mpad, void* Ab, int b32, double* yb, hipStream_t st) {
   const int64_t total = Npad_b * mpad;
   const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(total, 256), 65536);
-  hipLaunchKernelGGL(gather_rows_kernel, dim3(grid), dim3(256), 0, st, A, Npad, y, rows, n, Npad_b, mpad, Ab, yb);
+  if (b32 && !a32) return hipErrorInvalidValue;   // a batch is never narrower than its source
+  if (a32 && b32)
+    hipLaunchKernelGGL((gather_rows_kernel<float, float>), dim3(grid), dim3(256), 0, st, (const float*)A, Npad, y, rows,
+                       n, Npad_b, mpad, (float*)Ab, yb);
+  else if (a32)
+    hipLaunchKernelGGL((gather_rows_kernel<float, double>), dim3(grid), dim3(256), 0, st, (const float*)A, Npad, y,
+                       rows, n, Npad_b, mpad, (double*)Ab, yb);
+  else
+    hipLaunchKernelGGL((gather_rows_kernel<double, double>), dim3(grid), dim3(256), 0, st, (const double*)A, Npad, y,
+                       rows, n, Npad_b, mpad, (double*)Ab, yb);
   return hipGetLastError();
 }
 
 // panel p of A: column-major buffer C (Npad x 128, ld Npad) <-> the tiled blocks of panel p
-__global__ void retile_kernel(double* __restrict__ C, double* __restrict__ A, int64_t Npad, int64_t p, int to_tiled) {
+// (TC -> TA with to_tiled: a double C into a float A rounds to nearest even, the fp32 storage mode's
+// conversion of fp64 input; TA -> TC otherwise: widening)
+template <typename TC, typename TA>
+__global__ void retile_kernel(TC* __restrict__ C, TA* __restrict__ A, int64_t Npad, int64_t p, int to_tiled) {
   const int64_t S = Npad / 16;
-  double* blk = A + p * S * 128 * 16;
+  TA* blk = A + p * S * 128 * 16;
   for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < Npad * 128;
        e += (int64_t)gridDim.x * blockDim.x) {
     // e walks the tiled panel contiguously: e = (s*128 + f)*16 + ks
     const int64_t ks = e & 15, f = (e >> 4) & 127, s = e >> 11;
     const int64_t n = s * 16 + ks;
-    if (to_tiled) blk[e] = C[f * Npad + n];
-    else C[f * Npad + n] = blk[e];
+    if (to_tiled) blk[e] = (TA)C[f * Npad + n];
+    else C[f * Npad + n] = (TC)blk[e];
   }
 }
 
-hipError_t launch_retile(double* C, double* A, int64_t Npad, int64_t p, int to_tiled, hipStream_t st) {
-  hipLaunchKernelGGL(retile_kernel, dim3(1024), dim3(256), 0, st, C, A, Npad, p, to_tiled);
+hipError_t launch_retile(void* C, int c32, void* A, int a32, int64_t Npad, int64_t p, int to_tiled, hipStream_t st) {
+  if (c32 && !a32) return hipErrorInvalidValue;   // an fp32 staging buffer serves an fp32 A only
+  if (c32)
+    hipLaunchKernelGGL((retile_kernel<float, float>), dim3(1024), dim3(256), 0, st, (float*)C, (float*)A, Npad, p,
+                       to_tiled);
+  else if (a32)
+    hipLaunchKernelGGL((retile_kernel<double, float>), dim3(1024), dim3(256), 0, st, (double*)C, (float*)A, Npad, p,
+                       to_tiled);
+  else
+    hipLaunchKernelGGL((retile_kernel<double, double>), dim3(1024), dim3(256), 0, st, (double*)C, (double*)A, Npad, p,
+                       to_tiled);
   return hipGetLastError();
 }
 
@@ -294,7 +329,8 @@ constexpr int GT_ROWS = 4096;
 
 int gemv_t_chunks(int64_t Npad) { return (int)ceil_div(Npad, GT_ROWS); }
 
-__global__ __launch_bounds__(256) void gemv_t_kernel(const double* __restrict__ A, int64_t S, int64_t Npad,
+template <typename TA>
+__global__ __launch_bounds__(256) void gemv_t_kernel(const TA* __restrict__ A, int64_t S, int64_t Npad,
                                                      int64_t m, const double* __restrict__ v,
                                                      double* __restrict__ part, int64_t ldp) {
   __shared__ v2d vs[GT_ROWS / 2];
@@ -310,13 +346,13 @@ __global__ __launch_bounds__(256) void gemv_t_kernel(const double* __restrict__ 
     if (j >= m) break;
     v2d acc[4] = {{0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}};
     // columns j..j+3 share a panel (j % 4 == 0): rows of one stage are 16 contiguous samples
-    const double* p0 = A + tiled_off(S, r0, j);
+    const TA* p0 = A + tiled_off(S, r0, j);
     for (int i = lane; i < nh; i += 64) {
       const v2d vv = vs[i];
-      const double* pi = p0 + (int64_t)(i >> 3) * (128 * 16) + 2 * (i & 7);
+      const TA* pi = p0 + (int64_t)(i >> 3) * (128 * 16) + 2 * (i & 7);
 #pragma unroll
       for (int q = 0; q < 4; ++q)
-        if (j + q < m) acc[q] += *(const v2d*)(pi + 16 * q) * vv;
+        if (j + q < m) acc[q] += ld_pair(pi + 16 * q) * vv;
     }
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -331,21 +367,22 @@ __global__ __launch_bounds__(256) void gemv_t_kernel(const double* __restrict__ 
 // (f0, sc) takes features f0 + 32 k, samples 2 sc, 2 sc + 1 of every stage, then the 8 lanes of a
 // feature sum in a fixed butterfly.  The column-group kernel above reads each block as 2 x 4 x 4
 // scattered 512-B pieces (C2: 1.37 ms per pass, 4.8 TB/s).  SCS_GEMV_T=0: the column-group kernel.
-__global__ __launch_bounds__(256) void gemv_t_panel_kernel(const double* __restrict__ A, int64_t S, int64_t Npad,
+template <typename TA>
+__global__ __launch_bounds__(256) void gemv_t_panel_kernel(const TA* __restrict__ A, int64_t S, int64_t Npad,
                                                            int64_t m, const double* __restrict__ v,
                                                            double* __restrict__ part, int64_t ldp) {
   const int64_t r0 = (int64_t)blockIdx.x * GT_ROWS;
   const int ns = (int)(((Npad - r0 < GT_ROWS) ? Npad - r0 : GT_ROWS) / 16);   // Npad % 16 == 0
   const int tid = threadIdx.x, sc = tid & 7, f0 = tid >> 3;
-  const double* blk = A + ((int64_t)blockIdx.y * S + r0 / 16) * (128 * 16) + f0 * 16 + 2 * sc;
+  const TA* blk = A + ((int64_t)blockIdx.y * S + r0 / 16) * (128 * 16) + f0 * 16 + 2 * sc;
   const double* vp = v + r0 + 2 * sc;
   v2d acc[4] = {{0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}};
 #pragma unroll 4
   for (int s = 0; s < ns; ++s) {
     const v2d vv = *(const v2d*)(vp + 16 * s);
-    const double* b = blk + (int64_t)s * (128 * 16);
+    const TA* b = blk + (int64_t)s * (128 * 16);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) acc[k] += *(const v2d*)(b + 32 * 16 * k) * vv;
+    for (int k = 0; k < 4; ++k) acc[k] += ld_pair(b + 32 * 16 * k) * vv;
   }
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
@@ -363,15 +400,22 @@ static bool gemv_t_panel() {   // read per launch (A/B)
   return !(e && e[0] == '0');
 }
 
-hipError_t launch_gemv_t(const double* A, int64_t S, int64_t Npad, int64_t m, int64_t mpad, const double* v,
+hipError_t launch_gemv_t(const void* A, int a32, int64_t S, int64_t Npad, int64_t m, int64_t mpad, const double* v,
                          double* part, hipStream_t st) {
   if (gemv_t_panel()) {
-    hipLaunchKernelGGL(gemv_t_panel_kernel, dim3((unsigned)gemv_t_chunks(Npad), (unsigned)ceil_div(m, 128)), dim3(256),
-                       0, st, A, S, Npad, m, v, part, mpad);
+    const dim3 grid((unsigned)gemv_t_chunks(Npad), (unsigned)ceil_div(m, 128));
+    if (a32)
+      hipLaunchKernelGGL(gemv_t_panel_kernel<float>, grid, dim3(256), 0, st, (const float*)A, S, Npad, m, v, part, mpad);
+    else
+      hipLaunchKernelGGL(gemv_t_panel_kernel<double>, grid, dim3(256), 0, st, (const double*)A, S, Npad, m, v, part,
+                         mpad);
     return hipGetLastError();
   }
-  hipLaunchKernelGGL(gemv_t_kernel, dim3((unsigned)gemv_t_chunks(Npad), (unsigned)ceil_div(m, 64)), dim3(256), 0, st,
-                     A, S, Npad, m, v, part, mpad);
+  const dim3 grid((unsigned)gemv_t_chunks(Npad), (unsigned)ceil_div(m, 64));
+  if (a32)
+    hipLaunchKernelGGL(gemv_t_kernel<float>, grid, dim3(256), 0, st, (const float*)A, S, Npad, m, v, part, mpad);
+  else
+    hipLaunchKernelGGL(gemv_t_kernel<double>, grid, dim3(256), 0, st, (const double*)A, S, Npad, m, v, part, mpad);
   return hipGetLastError();
 }
 
@@ -424,24 +468,27 @@ __device__ __forceinline__ double gauss(uint64_t seed, uint64_t idx) {
   return sqrt(-2.0 * log(u1)) * cospi(2.0 * u2);
 }
 
-// grid.y = m_pad columns; columns >= m (and rows >= N) are zero
-__global__ void gen_A_kernel(double* __restrict__ A, int64_t Npad, int64_t N, int64_t m, int64_t row0,
+// grid.y = m_pad columns; columns >= m (and rows >= N) are zero; TA = float stores the fp64 value
+// rounded to nearest even
+template <typename TA>
+__global__ void gen_A_kernel(TA* __restrict__ A, int64_t Npad, int64_t N, int64_t m, int64_t row0,
                              uint64_t seed, double scale) {
   const int64_t j = blockIdx.y;
   const int64_t S = Npad / 16;
   for (int64_t n = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; n < Npad; n += (int64_t)gridDim.x * blockDim.x) {
     double v = 0.0;
     if (n < N && j < m) v = scale * gauss(seed, (uint64_t)(row0 + n) * (uint64_t)m + (uint64_t)j);
-    A[tiled_off(S, n, j)] = v;
+    A[tiled_off(S, n, j)] = (TA)v;
   }
 }
 
-hipError_t launch_gen_A(double* A, int64_t Npad, int64_t N, int64_t m, int64_t mpad, int64_t row0, uint64_t seed,
-                        double scale, hipStream_t st) {
+hipError_t launch_gen_A(void* A, int a32, int64_t Npad, int64_t N, int64_t m, int64_t mpad, int64_t row0,
+                        uint64_t seed, double scale, hipStream_t st) {
   int64_t gx = ceil_div(Npad, 256);
   if (gx > 64) gx = 64;
-  hipLaunchKernelGGL(gen_A_kernel, dim3((unsigned)gx, (unsigned)mpad), dim3(256), 0, st, A, Npad, N, m, row0, seed,
-                     scale);
+  const dim3 grid((unsigned)gx, (unsigned)mpad);
+  if (a32) hipLaunchKernelGGL(gen_A_kernel<float>, grid, dim3(256), 0, st, (float*)A, Npad, N, m, row0, seed, scale);
+  else hipLaunchKernelGGL(gen_A_kernel<double>, grid, dim3(256), 0, st, (double*)A, Npad, N, m, row0, seed, scale);
   return hipGetLastError();
 }
 
@@ -475,17 +522,20 @@ hipError_t launch_gen_y(int kind, const double* z, double* y, int64_t N, int64_t
 
 // out[k][n] = A(n, cols[k]) for n < N (column-major N x ncols): selected columns of the
 // panel-blocked A back in the host layout (bench.py's sampled Gram / Aᵀv check)
-__global__ void get_columns_kernel(const double* __restrict__ A, int64_t S, const int64_t* __restrict__ cols,
+template <typename TA>
+__global__ void get_columns_kernel(const TA* __restrict__ A, int64_t S, const int64_t* __restrict__ cols,
                                    int64_t N, double* __restrict__ out) {
   const int64_t k = blockIdx.y, j = cols[k];
   for (int64_t n = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; n < N; n += (int64_t)gridDim.x * blockDim.x)
-    out[k * N + n] = A[tiled_off(S, n, j)];
+    out[k * N + n] = (double)A[tiled_off(S, n, j)];
 }
 
-hipError_t launch_get_columns(const double* A, int64_t S, const int64_t* cols, int64_t ncols, int64_t N, double* out,
-                              hipStream_t st) {
+hipError_t launch_get_columns(const void* A, int a32, int64_t S, const int64_t* cols, int64_t ncols, int64_t N,
+                              double* out, hipStream_t st) {
   if (ncols <= 0 || N <= 0) return hipSuccess;
-  hipLaunchKernelGGL(get_columns_kernel, dim3(256, (unsigned)ncols), dim3(256), 0, st, A, S, cols, N, out);
+  const dim3 grid(256, (unsigned)ncols);
+  if (a32) hipLaunchKernelGGL(get_columns_kernel<float>, grid, dim3(256), 0, st, (const float*)A, S, cols, N, out);
+  else hipLaunchKernelGGL(get_columns_kernel<double>, grid, dim3(256), 0, st, (const double*)A, S, cols, N, out);
   return hipGetLastError();
 }
 

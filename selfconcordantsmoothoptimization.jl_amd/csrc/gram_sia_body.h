@@ -1,0 +1,269 @@
+// The body of gram_sia_kernel (gram.hip, which documents it), kept as text so that the kernel on an
+// fp32-stored A (gram_sia_ta_kernel) is the same statements over another element type.  In scope at
+// the point of inclusion: TA (element type of A), PIPE, TI, CM, AV, BND and the kernel's parameters.
+// Only the staging depends on TA: gload keeps the pairs as loaded and swrite widens them (exactly) on
+// their way to LDS; column-major operands are fp64.
+  static_assert(!(AV && CM), "the fused Aᵀv runs on the panel-blocked A only");
+  static_assert(!CM || sizeof(TA) == sizeof(double), "column-major operands are fp64");
+  constexpr int GTI = 64 * TI;        // tile rows (A1 features)
+  constexpr int NT = 128 * TI;        // threads
+  constexpr int FS = NT / 8;          // features per staging sweep
+  constexpr int NTI = 4;              // 16-row MFMA tiles per wave along i
+  constexpr int NA = GTI / FS;        // A1 staging chunks per thread per stage (4)
+  constexpr int NB = GT / FS;         // A2 staging chunks per thread per stage (4 or 2)
+  constexpr int NMM = 2 * NTI * 4;    // MFMAs per fragment set (2 u x NTI x 4)
+  constexpr int NRD = NTI + 4;        // ds_read_b128 per fragment set
+  constexpr int TAIL = NMM / 4;       // MFMAs left for phase 2b (1/8 and 3/8 measured within noise)
+  const int packed = flags & GRAM_PACKED, accumulate = flags & GRAM_ACCUMULATE, upper = flags & GRAM_UPPER;
+  __shared__ __attribute__((aligned(16))) double lds[(GTI + GT) * GBK];
+  const int orig = blockIdx.x;
+  const int xcd = orig % 8;
+  int bi, bj, tix, part = -1, piece = 0;
+  __shared__ int s_claim;
+  if constexpr (BND) {   // counters in scnt, skip mask in sob (bnd_first)
+    tix = bnd_first(scnt, (unsigned)sob, ntiles, &s_claim);
+    if (tix < 0 || tix >= ntiles) return;
+    bi = tiles[tix].x;
+    bj = tiles[tix].y;
+  } else if (work) {
+    const int4 it = work[xcd * seglen + orig / 8];
+    if (it.x < 0) return;
+    bi = it.x;
+    bj = it.y;
+    tix = it.w;
+    if (it.z >= 0) {
+      piece = it.z;
+      const int64_t L = ((Nk - k0 + (int64_t)nsplit * GBK - 1) / ((int64_t)nsplit * GBK)) * GBK;
+      part = it.w;
+      k0 = k0 + it.z * L;
+      Nk = k0 + L < Nk ? k0 + L : Nk;
+      if (Nk < k0) Nk = k0;
+    }
+  } else {
+    const int q8 = ntiles / 8, r8 = ntiles % 8;
+    tix = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + orig / 8;
+    const int2 tl = tiles[tix];
+    bi = tl.x;
+    bj = tl.y;
+  }
+bnd_tile:
+  int tid_ = threadIdx.x;
+  if constexpr (BND) asm volatile("" : "+v"(tid_));   // per tile: nothing derived from it is hoisted out of the loop
+  const int tid = tid_, lane = tid & 63, wid = tid >> 6;
+  const int wr = wid >> 1, wc = wid & 1;
+  const int sc = tid & 7, sf0 = tid >> 3;
+  const int64_t st0 = k0 / GBK;
+  // this thread's 16-B chunks of a stage: feature sf0 + FS i of the A1 rows (panel
+  // (GTI/128) bi + f/128) and of the A2 rows (panel bj), samples 2 sc, 2 sc + 1.
+  const TA* srcA = CM ? A + ((int64_t)bi * GTI + sf0) * S + k0 + 2 * sc
+                      : A + ((int64_t)bi * (GTI / GT) * S + st0) * GT * GBK + sf0 * GBK + 2 * sc;
+  // CM with A2: the A2 panels from a second column-major matrix (leading dimension S2; the LU's and
+  // the QR's two-operand products, the Cholesky's strip solves), else from A
+  const TA* B2 = (CM && A2) ? (const TA*)A2 : A;
+  const int64_t SB2 = (CM && A2) ? S2 : S;
+  const TA* srcB = CM ? B2 + ((int64_t)bj * GT + sf0) * SB2 + k0 + 2 * sc
+                      : A + ((int64_t)bj * S + st0) * GT * GBK + sf0 * GBK + 2 * sc;
+  const double* srcW = w + k0 + 2 * sc;
+  const double* srcV = AV ? v + k0 + 2 * sc : nullptr;
+  double* la = lds;
+  double* lb = lds + GTI * GBK;
+  int woff[NA];
+#pragma unroll
+  for (int i = 0; i < NA; ++i) {
+    const int f = sf0 + FS * i;
+    woff[i] = f * GBK + 2 * (sc ^ swz(f));
+  }
+  // the staged chunks as loaded (TA pairs): an fp32-stored A is widened when they are written to LDS
+  typedef typename pair_of<TA>::type PR;
+  PR ra[NA], rb[NB];
+  v2d rw, rv;
+  double av[NB];
+#pragma unroll
+  for (int i = 0; i < NB; ++i) av[i] = 0.0;
+  // fa: std::bool_constant -- the designated tiles of an AV launch run the loop with the Aᵀv
+  // products (FA), every other tile the plain loop (no extra loads or VALU)
+  auto gload = [&](int64_t st, auto fa) {
+    constexpr bool FA = decltype(fa)::value;
+    if (PIPE == 3 && st >= 2) return;   // timing build: no global loads after the prologue
+    if (CM) {
+#pragma unroll
+      for (int i = 0; i < NA; ++i) ra[i] = *(const PR*)(srcA + st * GBK + (int64_t)FS * i * S);
+#pragma unroll
+      for (int i = 0; i < NB; ++i) rb[i] = *(const PR*)(srcB + st * GBK + (int64_t)FS * i * SB2);
+    } else {
+      const int64_t so = st * GT * GBK;
+#pragma unroll
+      for (int i = 0; i < NA; ++i) {
+        const int f = FS * i;   // + sf0 (in srcA): the panel of f is f / 128 (FS divides 128)
+        ra[i] = *(const PR*)(srcA + so + (f >> 7) * S * GT * GBK + (f & 127) * GBK);
+      }
+#pragma unroll
+      for (int i = 0; i < NB; ++i) rb[i] = *(const PR*)(srcB + so + FS * GBK * i);
+    }
+    rw = *(const v2d*)(srcW + st * GBK);
+    if (FA) rv = *(const v2d*)(srcV + st * GBK);
+  };
+  auto swrite = [&](auto fa) {
+    constexpr bool FA = decltype(fa)::value;
+#pragma unroll
+    for (int i = 0; i < NA; ++i) *(v2d*)(la + woff[i]) = widen(ra[i]);
+#pragma unroll
+    for (int i = 0; i < NB; ++i) *(v2d*)(lb + woff[i]) = widen(rb[i]) * rw;
+    if (FA) {
+#pragma unroll
+      for (int i = 0; i < NB; ++i) {
+        const v2d b = widen(rb[i]);
+        av[i] = __builtin_fma(b[1], rv[1], __builtin_fma(b[0], rv[0], av[i]));
+      }
+    }
+  };
+  const int fl = lane & 15, g = lane >> 4, s = swz(fl);
+  struct Frag {
+    v2d a[NTI], b[4];
+  };
+  auto fread = [&](int p, Frag& F) {
+    const int pc = ((4 * p + g) ^ s) * 2;
+#pragma unroll
+    for (int t = 0; t < NTI; ++t) F.a[t] = *(const v2d*)(la + (wr * 64 + 16 * t + fl) * GBK + pc);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) F.b[t] = *(const v2d*)(lb + (wc * 64 + 16 * t + fl) * GBK + pc);
+  };
+  v4d acc[NTI][4];
+#pragma unroll
+  for (int i = 0; i < NTI; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = (v4d){0.0, 0.0, 0.0, 0.0};
+  // MFMAs n in [n0, n1) of a fragment set, n = 4 NTI u + 4 ti + tj (the plain loop's order)
+  auto mm = [&](const Frag& F, int n0, int n1) {
+#pragma unroll
+    for (int n = n0; n < n1; ++n) {
+      const int u = n / (4 * NTI), ti = (n / 4) % NTI, tj = n & 3;
+      acc[ti][tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(F.a[ti][u], F.b[tj][u], acc[ti][tj], 0, 0, 0);
+    }
+  };
+  auto barrier = [&]() {   // also a scheduling fence: nothing (e.g. the w products) crosses a phase
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): this wave's LDS traffic is done
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  const int nk = (int)((Nk - k0) / GBK);
+  Frag F0, F1;
+  auto run = [&](auto fa) {
+    if (nk > 0) {
+      gload(0, fa);
+      swrite(fa);
+      if (nk > 1) gload(1, fa);
+      barrier();
+      fread(0, F0);
+    }
+    auto body = [&](int k, bool has1, bool has2) {
+      // phase 1
+      __builtin_amdgcn_sched_barrier(0);
+      fread(1, F1);
+      mm(F0, 0, NMM);
+      if (PIPE) {
+#pragma unroll
+        for (int i = 0; i < NRD; ++i) {
+          __builtin_amdgcn_sched_group_barrier(0x008, NMM / NRD, 0);   // MFMA
+          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);           // DS read
+        }
+      }
+      barrier();
+      // phase 2a
+      if (has1) swrite(fa);
+      if (has2) gload(k + 2, fa);
+      mm(F1, 0, NMM - TAIL);
+      if (PIPE) {
+        if (has1) {
+#pragma unroll
+          for (int i = 0; i < NA + NB; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, (NMM - TAIL) / (NA + NB), 0);   // MFMA
+            __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);                         // DS write
+            if (has2) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);               // VMEM read
+          }
+        }
+        __builtin_amdgcn_sched_group_barrier(0x008, NMM, 0);
+      }
+      // phase 2b
+      if (has1) {
+        barrier();
+        fread(0, F0);
+      }
+      mm(F1, NMM - TAIL, NMM);
+      if (PIPE && has1) {
+#pragma unroll
+        for (int i = 0; i < NRD; ++i) {
+          __builtin_amdgcn_sched_group_barrier(0x008, TAIL / NRD > 0 ? TAIL / NRD : 1, 0);
+          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+        }
+      }
+    };
+    int k = 0;
+    for (; k + 2 < nk; ++k) body(k, true, true);
+    if (k + 1 < nk) {
+      body(k, true, false);
+      ++k;
+    }
+    if (k < nk) body(k, false, false);
+  };
+  const bool dav = AV && (int64_t)bj * GT / GTI == bi;   // this tile owns panel bj's Aᵀv rows
+  if constexpr (AV) {
+    if (dav) run(std::true_type{});
+    else run(std::false_type{});
+  } else {
+    run(std::false_type{});
+  }
+
+  if (dav) {   // lanes 8q .. 8q+7 share a feature
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+      double t = av[i];
+      t += __shfl_xor(t, 1);
+      t += __shfl_xor(t, 2);
+      t += __shfl_xor(t, 4);
+      if (sc == 0) VP[(int64_t)piece * vps + (int64_t)bj * GT + sf0 + FS * i] = t;
+    }
+  }
+
+  // epilogue (the C/D map of gram_f64_kernel): element (il, jl) of the GTI x 128 tile
+  if constexpr (BND || CM) {   // the persistent and gen-form launches: old values loaded ahead of the stores
+#pragma unroll
+    for (int ti = 0; ti < NTI; ++ti)
+      gram_tile_store_row(acc[ti], ti, wr, wc, g, fl, part, P, GTI, packed, upper, accumulate, G, ldg, tix, bi, bj);
+  } else {
+#pragma unroll
+    for (int ti = 0; ti < NTI; ++ti)
+#pragma unroll
+      for (int tj = 0; tj < 4; ++tj)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int il = wr * 64 + 16 * ti + g + 4 * r;
+          const int jl = wc * 64 + 16 * tj + fl;
+          double* dst;
+          if (part >= 0) {
+            P[((int64_t)part * GT + jl) * GTI + il] = acc[ti][tj][r];
+            continue;
+          }
+          if (packed) dst = G + ((int64_t)tix * (GTI / GT) + il / GT) * GT * GT + jl * GT + (il % GT);
+          else if (upper) dst = G + ((int64_t)bi * GTI + il) * ldg + (int64_t)bj * GT + jl;
+          else dst = G + ((int64_t)bj * GT + jl) * ldg + (int64_t)bi * GTI + il;
+          if (accumulate) *dst += acc[ti][tj][r];
+          else *dst = acc[ti][tj][r];
+        }
+  }
+  // strip completion (scsopt.cpp gram_factor_pipelined, one-launch mode): this tile's rows lie in
+  // outer strip bj / sob; each thread's stores are released to device scope before one count
+  if (!BND && scnt && part < 0) {
+    __threadfence();
+    __syncthreads();
+    if (tid == 0) atomicAdd(scnt + bj / sob, 1u);
+  }
+  if constexpr (BND) {
+    tix = bnd_next(scnt, ntiles, &s_claim);
+    if (tix >= ntiles) return;
+    bi = tiles[tix].x;
+    bj = tiles[tix].y;
+    goto bnd_tile;
+  }

@@ -34,7 +34,9 @@ void gram_tile_list_tall(int nb, int2* out, int* ntiles);
 // nsplit > 1), reduced by gram_vfinal_launch.
 // rocprofv3's name of the kernel the latest gram_launch / gram_launch_sched ran
 const char* gram_main_kernel_name();
-hipError_t gram_launch(const double* A, int64_t lda, const double* w, int64_t Nk, const int2* tiles, int ntiles,
+// a32 (next to A, here and in gram_launch_sched): A is stored fp32 (scs_set_dense_f32) -- the default
+// interleaved kernels on float elements, whatever SCS_GRAM_SIA / SCS_GRAM_GLDS select for fp64
+hipError_t gram_launch(const void* A, int a32, int64_t lda, const double* w, int64_t Nk, const int2* tiles, int ntiles,
                        double* G, int64_t ldg, int packed, int tall, hipStream_t st, const double* v = nullptr,
                        double* VP = nullptr, int64_t vps = 0);
 int gram_fuse_ok(int tall);
@@ -60,9 +62,9 @@ hipError_t gram_launch_small(const double* A1, int64_t lda1, const double* A2, i
 // combine items (bi, bj, tix, first partial slot)
 int gram_schedule(const int2* tiles, int ntiles, int slots_per_xcd, std::vector<int4>& work, std::vector<int4>& comb,
                   int* nsplit, int* npart, int diag_first_gti = 0);
-hipError_t gram_launch_sched(const double* A, int64_t lda, const double* w, int64_t Nk, const int4* work, int seglen,
-                             int nsplit, const int4* comb, int ncomb, double* P, double* G, int64_t ldg, int packed,
-                             int tall, hipStream_t st, const double* v = nullptr, double* VP = nullptr,
+hipError_t gram_launch_sched(const void* A, int a32, int64_t lda, const double* w, int64_t Nk, const int4* work,
+                             int seglen, int nsplit, const int4* comb, int ncomb, double* P, double* G, int64_t ldg,
+                             int packed, int tall, hipStream_t st, const double* v = nullptr, double* VP = nullptr,
                              int64_t vps = 0, unsigned* scnt = nullptr, int sob = 0);
 // scnt: per-strip completion counts (each finished whole tile adds 1 to scnt[bj / sob]); the
 // factor stream waits for a strip with strip_wait_launch (flag: set on a timed-out wait)
@@ -338,8 +340,10 @@ hipError_t launch_rosen(const double* x, int64_t m, int what, double* out, doubl
 // ---- data.hip
 // z-partials: out[split][ldo] ; returns the number of splits used
 int gemv_n_splits(int64_t Npad, int64_t m);
-// A is panel-blocked (common.h tiled_off), S = Npad / 16; x has m_pad entries (zero beyond m)
-hipError_t launch_gemv_n(const double* A, int64_t S, int64_t Npad, int64_t mpad, const double* x, int nsplit,
+// A is panel-blocked (common.h tiled_off), S = Npad / 16; x has m_pad entries (zero beyond m).
+// a32 next to a panel-blocked pointer (here and below): its elements are float (scs_set_dense_f32),
+// widened on load -- fp64 arithmetic in the fp64 kernel's order
+hipError_t launch_gemv_n(const void* A, int a32, int64_t S, int64_t Npad, int64_t mpad, const double* x, int nsplit,
                          double* part, int64_t ldo, hipStream_t st);
 // loss epilogue over samples: sums the z-partials, writes z / coefficient vectors and
 // per-block loss partials.  Returns the number of value partials written.
@@ -358,10 +362,11 @@ hipError_t launch_ls_pair(const double* z0, const double* zd, double alpha, int6
                           hipStream_t st);
 // Aᵀ v (column partial sums over row chunks, then a fixed-order finalize)
 int gemv_t_chunks(int64_t Npad);
-hipError_t launch_gemv_t(const double* A, int64_t S, int64_t Npad, int64_t m, int64_t mpad, const double* v,
+hipError_t launch_gemv_t(const void* A, int a32, int64_t S, int64_t Npad, int64_t m, int64_t mpad, const double* v,
                          double* part, hipStream_t st);
-// panel p: column-major Npad x 128 buffer C <-> tiled A (to_tiled = 1: C -> A)
-hipError_t launch_retile(double* C, double* A, int64_t Npad, int64_t p, int to_tiled, hipStream_t st);
+// panel p: column-major Npad x 128 buffer C <-> tiled A (to_tiled = 1: C -> A; a double C into a float A
+// rounds to nearest even; c32: C holds floats, a32 only)
+hipError_t launch_retile(void* C, int c32, void* A, int a32, int64_t Npad, int64_t p, int to_tiled, hipStream_t st);
 // out[j] = Σ_chunk part[chunk][j] (+ lam*add[j] if add)
 hipError_t launch_gemv_t_finalize(const double* part, int nchunk, int64_t mpad, int64_t m, double* out,
                                   hipStream_t st);
@@ -372,13 +377,13 @@ hipError_t launch_densify_range(const int64_t* rowptr, const int* col, const voi
                                 int64_t n, int64_t Npad_b, int zero, double* Ab, hipStream_t st);
 hipError_t launch_densify_rows(const int64_t* rowptr, const int* col, const void* val, int f32, const int64_t* rows,
                                int64_t n, int64_t Npad_b, const double* y, double* Ab, double* yb, hipStream_t st);
-hipError_t launch_gather_rows(const double* A, int64_t Npad, const double* y, const int64_t* rows, int64_t n,
-                              int64_t Npad_b, int64_t mpad, double* Ab, double* yb, hipStream_t st);
-hipError_t launch_transpose(const double* A, int64_t Npad, int64_t N, int64_t m, double* At, int64_t ldt,
+hipError_t launch_gather_rows(const void* A, int a32, int64_t Npad, const double* y, const int64_t* rows, int64_t n,
+                              int64_t Npad_b, int64_t mpad, void* Ab, int b32, double* yb, hipStream_t st);
+hipError_t launch_transpose(const void* A, int a32, int64_t Npad, int64_t N, int64_t m, double* At, int64_t ldt,
                             int64_t nt, hipStream_t st);
 // selected columns of the panel-blocked A -> column-major N x ncols (cols on the device)
-hipError_t launch_get_columns(const double* A, int64_t S, const int64_t* cols, int64_t ncols, int64_t N, double* out,
-                              hipStream_t st);
+hipError_t launch_get_columns(const void* A, int a32, int64_t S, const int64_t* cols, int64_t ncols, int64_t N,
+                              double* out, hipStream_t st);
 // out[k] = G(ij[k].x, ij[k].y) of a column-major matrix
 hipError_t launch_gather_entries(const double* G, int64_t ld, const int2* ij, int n, double* out, hipStream_t st);
 // GGN sample-space branch (vec.hip)
@@ -392,8 +397,8 @@ hipError_t launch_ggn_sample_scale(const double* s, const double* B, int64_t N, 
 hipError_t launch_ggn_sample_direction(const double* hvec, const double* t, const double* hg, const double* B,
                                        int64_t N, int64_t m, double* d, hipStream_t st);
 // synthetic data
-hipError_t launch_gen_A(double* A, int64_t Npad, int64_t N, int64_t m, int64_t mpad, int64_t row0, uint64_t seed,
-                        double scale, hipStream_t st);
+hipError_t launch_gen_A(void* A, int a32, int64_t Npad, int64_t N, int64_t m, int64_t mpad, int64_t row0,
+                        uint64_t seed, double scale, hipStream_t st);
 hipError_t launch_gen_xtrue(double* x, int64_t m, uint64_t seed, double density, hipStream_t st);
 hipError_t launch_gen_y(int kind, const double* z, double* y, int64_t N, int64_t row0, uint64_t seed,
                         hipStream_t st);

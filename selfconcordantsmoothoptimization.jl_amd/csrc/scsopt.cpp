@@ -64,6 +64,7 @@ struct DevBuf {
 // duration of scs_step (the As, ys handed to step!, iterate.jl:205-207).
 struct NView {
   double* A = nullptr;
+  int a32 = 0;   // A holds float elements (scs_set_dense_f32): half the doubles allocated, widened on load
   double* y = nullptr;
   int64_t N = 0, Npad = 0, nstage = 0, Nglob = 0;
   int nsplit = 1, nval = 1, nchunk = 1;
@@ -103,6 +104,10 @@ struct scs_ctx {
   bool has_data = false;
   bool generic = false;  // ProblemGeneric (no A)
   double* A = nullptr;
+  // fp32 storage of the dense row blocks (scs_set_dense_f32): a32 says what A holds now (it follows the
+  // swapped-in view), dense_f32 is the mode of the blocks uploaded or generated next; the arithmetic
+  // stays fp64 (f32c below is independent of both)
+  int a32 = 0, dense_f32 = 0;
   double* y = nullptr;
   // sparse A: CSR (rows) + CSC copy (columns), values fp64 or fp32
   bool sparse = false;
@@ -859,11 +864,21 @@ void invalidate_caches(scs_ctx* c) {
 // f / ∇f building blocks
 // ---------------------------------------------------------------------------
 // finalize a loss sum: the per-kind constant of f (see epilogue_kernel)
+// a panel-blocked block of `rows` (padded) rows: bytes, and its allocation (a float block is kept
+// in the double-typed field, rows * mpad / 2 doubles; mpad % 128 == 0)
+size_t a_block_bytes(const scs_ctx* c, int64_t rows, int a32) {
+  return (size_t)rows * c->mpad * (a32 ? sizeof(float) : sizeof(double));
+}
+double* alloc_A(scs_ctx* c, int64_t rows, int a32) {
+  return dalloc<double>(c, a_block_bytes(c, rows, a32) / sizeof(double));
+}
+
 // exchange the context's N-dependent fields with v (the full data <-> a minibatch)
 void swap_view(scs_ctx* c, NView& v) {
   ++c->data_gen;
   std::swap(c->sparse, v.sparse);
   std::swap(c->A, v.A);
+  std::swap(c->a32, v.a32);
   std::swap(c->y, v.y);
   std::swap(c->N, v.N);
   std::swap(c->Npad, v.Npad);
@@ -994,7 +1009,8 @@ void select_batch(scs_ctx* c, int64_t b) {
     // rows >= N, so it contributes nothing to the exchanged sums)
     v.Npad = round_up(std::max<int64_t>(n, 1), 16);
     v.nstage = v.Npad / 16;
-    v.A = dalloc<double>(c, (size_t)v.Npad * c->mpad);
+    v.a32 = c->sparse ? 0 : c->a32;   // a batch of an fp32-stored A is fp32; the dense batch of a sparse A fp64
+    v.A = alloc_A(c, v.Npad, v.a32);
     v.y = dalloc<double>(c, v.Npad);
     swap_view(c, v);
     alloc_nspace(c);
@@ -1006,17 +1022,18 @@ void select_batch(scs_ctx* c, int64_t b) {
   if (c->bheld[k] != b) {
     NView& v = c->bpool[k];
     if (n == 0) {
-      HCK(hipMemsetAsync(v.A, 0, sizeof(double) * (size_t)v.Npad * c->mpad, c->st));
+      HCK(hipMemsetAsync(v.A, 0, a_block_bytes(c, v.Npad, v.a32), c->st));
       HCK(hipMemsetAsync(v.y, 0, sizeof(double) * v.Npad, c->st));
     } else if (c->sparse) {   // CSR rows -> the dense batch (the reference's Matrix(As') of a sparse A)
       HCK(hipMemsetAsync(v.A, 0, sizeof(double) * (size_t)v.Npad * c->mpad, c->st));
       HCK(launch_densify_rows(c->rowptr, c->colidx, c->val, c->sp_f32, c->brows + c->boff[b], n, v.Npad, c->y,
                               v.A, v.y, c->st));
     } else {
-      HCK(launch_gather_rows(c->A, c->Npad, c->y, c->brows + c->boff[b], n, v.Npad, c->mpad, v.A, v.y, c->st));
+      HCK(launch_gather_rows(c->A, c->a32, c->Npad, c->y, c->brows + c->boff[b], n, v.Npad, c->mpad, v.A, v.a32, v.y,
+                             c->st));
     }
     // the view's GGN sample-space Aᵀ copy (built once per A, ggn_sample_step) follows its rows
-    if (v.At) HCK(launch_transpose(v.A, v.Npad, n, c->m, v.At, c->mpad, v.NpS, c->st));
+    if (v.At) HCK(launch_transpose(v.A, v.a32, v.Npad, n, c->m, v.At, c->mpad, v.NpS, c->st));
     c->bheld[k] = b;
   }
   c->bview = k;
@@ -1031,6 +1048,9 @@ double loss_scale_value(scs_ctx* c, double s) {
   }
 }
 
+// rocprofv3's name of the A x kernel on an fp32-stored dense A (scs_kernel_names)
+const char* const GEMV_N_F32_NAME = "gemv_n_kernel<float>";
+
 // z-partials of A x into c->zpart (dense: `nsplit` column splits; sparse: one
 // CSR gather pass).  Returns the number of partials written.
 int matvec_n(scs_ctx* c, const double* xd, int nsplit) {
@@ -1041,7 +1061,8 @@ int matvec_n(scs_ctx* c, const double* xd, int nsplit) {
     c->prod_kname = spmv_kernel_name(vk);
     return B.nblk;
   }
-  HCK(launch_gemv_n(c->A, c->nstage, c->Npad, c->mpad, xd, nsplit, c->zpart, c->Npad, c->st));
+  HCK(launch_gemv_n(c->A, c->a32, c->nstage, c->Npad, c->mpad, xd, nsplit, c->zpart, c->Npad, c->st));
+  if (c->a32) c->prod_kname = GEMV_N_F32_NAME;
   return nsplit;
 }
 
@@ -1053,7 +1074,7 @@ int matvec_t_part(scs_ctx* c, const double* v) {
     HCK(launch_spmv_blk(B.ptr, B.lidx, B.val, vk, v, c->m, c->N, B.shift, c->nnz, c->tpart, c->mpad, c->st));
     return B.nblk;
   }
-  HCK(launch_gemv_t(c->A, c->nstage, c->Npad, c->m, c->mpad, v, c->tpart, c->st));
+  HCK(launch_gemv_t(c->A, c->a32, c->nstage, c->Npad, c->m, c->mpad, v, c->tpart, c->st));
   return c->nchunk;
 }
 
@@ -1067,6 +1088,7 @@ void matvec_t(scs_ctx* c, const double* v, double* out) {
 void require_dense(scs_ctx* c, const char* what) {
   if (c->sparse)
     fail(c, SCS_ERR_ARG, "%s needs a dense A (sparse A supports f, ∇f and ProxLQNSCORE)", what);
+  if (c->a32) fail(c, SCS_ERR_ARG, "%s needs an fp64-stored A: fp32 storage (scs_set_dense_f32) does not cover it", what);
 }
 
 // Forward pass at the device vector xd whose host copy is xh: z = A x (or the
@@ -1170,7 +1192,7 @@ double eval_f_dev(scs_ctx* c, const double* xh, const double* xd) {
   if (c->loss == SCS_LOSS_QUADRATIC) {
     // 1/2*(x'*(A*x)) + y'*x
     require_dense(c, "the quadratic loss");
-    HCK(launch_gemv_n(c->A, c->nstage, c->Npad, c->mpad, xd, 1, c->zpart, c->Npad, c->st));
+    HCK(launch_gemv_n(c->A, 0, c->nstage, c->Npad, c->mpad, xd, 1, c->zpart, c->Npad, c->st));
     HCK(launch_dot(xd, c->zpart, c->m, c->scal + 8, c->st));
     HCK(launch_dot(c->y, xd, c->m, c->scal + 9, c->st));
     d2h(c, c->hscal + 8, c->scal + 8, 2);
@@ -1234,7 +1256,7 @@ void grad_f_dev(scs_ctx* c, const double* xh, const double* xd, double* out, int
   if (c->loss == SCS_LOSS_QUADRATIC) {
     // 0.5*(A*x + Aᵀ*x) + y
     require_dense(c, "the quadratic loss");
-    HCK(launch_gemv_n(c->A, c->nstage, c->Npad, c->mpad, xd, 1, c->zpart, c->Npad, c->st));
+    HCK(launch_gemv_n(c->A, 0, c->nstage, c->Npad, c->mpad, xd, 1, c->zpart, c->Npad, c->st));
     gemv_t_global(c, xd, c->gtmp2);
     HCK(launch_axpby(c->zpart, 1.0, c->gtmp2, c->m, c->gtmp2, c->st));
     HCK(launch_axpby(c->y, 0.5, c->gtmp2, c->m, out, c->st));  // y + 0.5*(Ax + Aᵀx)
@@ -1618,6 +1640,8 @@ bool solve_factored(scs_ctx* c, double* rhs, hipEvent_t e0) {
 // the panel-blocked A the Gram kernels read: A itself, or for a sparse A its dense mirror, built
 // once (Jt*Q*Jt' of a SparseMatrixCSC, prox-GGN-SCORE.jl:129 / hess_fx, prox-N-SCORE.jl:55; the
 // products Ax, Aᵀv keep running on the sparse copies)
+// (dense_a32: what that block holds -- the mirror of a sparse A is always fp64)
+int dense_a32(const scs_ctx* c) { return c->sparse ? 0 : c->a32; }
 const double* dense_A(scs_ctx* c) {
   if (!c->sparse) return c->A;
   if (c->Ad) return c->Ad;
@@ -1806,10 +1830,10 @@ void gram_main_stream(scs_ctx* c, const double* w, double* out, int packed) {
     const int mode = packed | (k > 0 ? 2 : 0);
     const int64_t nk = round_up(std::max<int64_t>(n, 1), 16);   // w + r0 + nk <= w + Npad
     if (c->gwork)
-      HCK(gram_launch_sched(slot, R / 16, w + r0, nk, c->gwork, c->gseglen, c->gnsplit, c->gcomb, c->gncomb, c->gpart,
+      HCK(gram_launch_sched(slot, 0, R / 16, w + r0, nk, c->gwork, c->gseglen, c->gnsplit, c->gcomb, c->gncomb, c->gpart,
                             out, c->mpad, mode, c->tall, c->st));
     else
-      HCK(gram_launch(slot, R / 16, w + r0, nk, c->tiles, c->ntiles, out, c->mpad, mode, c->tall, c->st));
+      HCK(gram_launch(slot, 0, R / 16, w + r0, nk, c->tiles, c->ntiles, out, c->mpad, mode, c->tall, c->st));
     c->gram_kname = gram_main_kernel_name();
   }
 }
@@ -1831,11 +1855,11 @@ void gram_main(scs_ctx* c, const double* w, double* out, int packed, const doubl
   const int npiece = (v && c->gwork) ? std::max(c->gnsplit, 1) : 1;
   if (v && npiece > 1) HCK(hipMemsetAsync(c->vpart, 0, sizeof(double) * npiece * c->mpad, c->st));
   if (c->gwork)
-    HCK(gram_launch_sched(A, c->nstage, w, c->Npad, c->gwork, c->gseglen, c->gnsplit, c->gcomb, c->gncomb, c->gpart,
-                          out, c->mpad, packed, c->tall, c->st, v, c->vpart, c->mpad));
+    HCK(gram_launch_sched(A, dense_a32(c), c->nstage, w, c->Npad, c->gwork, c->gseglen, c->gnsplit, c->gcomb, c->gncomb,
+                          c->gpart, out, c->mpad, packed, c->tall, c->st, v, c->vpart, c->mpad));
   else
-    HCK(gram_launch(A, c->nstage, w, c->Npad, c->tiles, c->ntiles, out, c->mpad, packed, c->tall, c->st, v, c->vpart,
-                    c->mpad));
+    HCK(gram_launch(A, dense_a32(c), c->nstage, w, c->Npad, c->tiles, c->ntiles, out, c->mpad, packed, c->tall, c->st,
+                    v, c->vpart, c->mpad));
   c->gram_kname = gram_main_kernel_name();
   if (v) HCK(gram_vfinal_launch(c->vpart, npiece, c->mpad, c->m, vout, c->st));
 }
@@ -1951,14 +1975,14 @@ hipEvent_t gram_factor_pipelined(scs_ctx* c, const double* w, const double* v, d
   HCK(hipStreamWaitEvent(c->sf, c->evstrip[ns], 0));
   if (one) {
     const scs_ctx::GStrip& g = c->gpipe;
-    HCK(gram_launch_sched(A, c->nstage, w, c->Npad, g.work, g.seglen, g.nsplit, g.comb, g.ncomb, c->gpart, c->G, ld,
-                          0, c->tall, c->st, fuse ? v : nullptr, c->vpart, ld, c->gp_cnt, OB));
+    HCK(gram_launch_sched(A, dense_a32(c), c->nstage, w, c->Npad, g.work, g.seglen, g.nsplit, g.comb, g.ncomb, c->gpart,
+                          c->G, ld, 0, c->tall, c->st, fuse ? v : nullptr, c->vpart, ld, c->gp_cnt, OB));
     HCK(hipEventRecord(c->evstrip[ns - 1], c->st));   // the last strip (and its combined pieces)
   } else {
     for (int s2 = 0; s2 < ns; ++s2) {
       const scs_ctx::GStrip& g = c->gstrip[s2];
-      HCK(gram_launch_sched(A, c->nstage, w, c->Npad, g.work, g.seglen, g.nsplit, g.comb, g.ncomb, c->gpart, c->G, ld,
-                            0, c->tall, c->st, fuse ? v : nullptr, c->vpart, ld));
+      HCK(gram_launch_sched(A, dense_a32(c), c->nstage, w, c->Npad, g.work, g.seglen, g.nsplit, g.comb, g.ncomb, c->gpart,
+                            c->G, ld, 0, c->tall, c->st, fuse ? v : nullptr, c->vpart, ld));
       HCK(hipEventRecord(c->evstrip[s2], c->st));
     }
   }
@@ -2035,7 +2059,9 @@ void ggn_sample_direction_sharded(scs_ctx* c, const double* xh) {
     }
     int64_t* drows = dalloc<int64_t>(c, Ng);
     HCK(hipMemcpyAsync(drows, rows.data(), sizeof(int64_t) * Ng, hipMemcpyHostToDevice, c->st));
-    HCK(launch_gather_rows(c->A, c->Npad, c->y, drows, Ng, Npg, c->mpad, c->red, c->red + Npg * c->mpad, c->st));
+    // (an fp32-stored A is widened into the fp64 reduce buffer: the gathered view is fp64, at most m x m)
+    HCK(launch_gather_rows(c->A, c->a32, c->Npad, c->y, drows, Ng, Npg, c->mpad, c->red, 0, c->red + Npg * c->mpad,
+                           c->st));
     allreduce(c, c->red, Npg * c->mpad + Npg);
     NView& v = c->gview;
     const bool fresh = !c->gview_ok;   // same size as the view held: refill its buffers in place
@@ -2049,7 +2075,7 @@ void ggn_sample_direction_sharded(scs_ctx* c, const double* xh) {
     HCK(hipMemcpyAsync(v.A, c->red, sizeof(double) * Npg * c->mpad, hipMemcpyDeviceToDevice, c->st));
     HCK(hipMemcpyAsync(v.y, c->red + Npg * c->mpad, sizeof(double) * Npg, hipMemcpyDeviceToDevice, c->st));
     // a refilled view's Aᵀ copy (built once per A by ggn_sample_direction) follows its rows
-    if (!fresh && v.At) HCK(launch_transpose(v.A, v.Npad, Ng, c->m, v.At, c->mpad, v.NpS, c->st));
+    if (!fresh && v.At) HCK(launch_transpose(v.A, 0, v.Npad, Ng, c->m, v.At, c->mpad, v.NpS, c->st));
     sync(c);
     dfree_t(c, drows);
     if (fresh) {
@@ -2085,12 +2111,12 @@ void ggn_sample_direction(scs_ctx* c, const double* xh) {
   const int64_t N = c->N, m = c->m;
   if (sharded(c)) return ggn_sample_direction_sharded(c, xh);
   if (c->At && c->loss == SCS_LOSS_CALLBACK)   // the caller's J changes every step
-    HCK(launch_transpose(c->A, c->Npad, N, m, c->At, c->mpad, c->NpS, c->st));
+    HCK(launch_transpose(c->A, c->a32, c->Npad, N, m, c->At, c->mpad, c->NpS, c->st));
   if (!c->At) {
     const double* A = dense_A(c);
     c->NpS = round_up(N, 128);
     c->At = dalloc<double>(c, (size_t)c->NpS * c->mpad);
-    HCK(launch_transpose(A, c->Npad, N, m, c->At, c->mpad, c->NpS, c->st));
+    HCK(launch_transpose(A, dense_a32(c), c->Npad, N, m, c->At, c->mpad, c->NpS, c->st));
     c->Ps = dalloc<double>(c, (size_t)c->NpS * c->NpS);
     c->n1pad = round_up(N + 1, 128);   // row-major, zero padding (lu.hip)
     c->Ms = dalloc<double>(c, (size_t)c->n1pad * c->n1pad);
@@ -2156,16 +2182,19 @@ void ggn_sample_direction(scs_ctx* c, const double* xh) {
 }
 
 // host column-major rows (N x m, lda) -> panel-blocked dst (Npad x mpad), one 128-column panel
-// at a time through the column-major staging buffer C (Npad x 128)
-static void upload_panels(scs_ctx* c, const double* A, int64_t N, int64_t lda, int64_t Npad, double* dst, double* C) {
+// at a time through the column-major staging buffer C (Npad x 128).  in32: the host rows (and C's
+// elements) are float; a32: dst's are -- fp64 rows into an fp32 dst are rounded in the retile step
+static void upload_panels(scs_ctx* c, const void* A, int in32, int64_t N, int64_t lda, int64_t Npad, double* dst,
+                          int a32, double* C) {
   const int64_t m = c->m;
+  const size_t es = in32 ? sizeof(float) : sizeof(double);
   for (int64_t p = 0; p < c->mpad / 128; ++p) {
     const int64_t j0 = p * 128, nc = std::min<int64_t>(128, m - j0);
-    HCK(hipMemsetAsync(C, 0, sizeof(double) * Npad * 128, c->st));
+    HCK(hipMemsetAsync(C, 0, es * Npad * 128, c->st));
     if (nc > 0 && N > 0)
-      HCK(hipMemcpy2DAsync(C, sizeof(double) * Npad, A + j0 * lda, sizeof(double) * lda, sizeof(double) * N, nc,
-                           hipMemcpyHostToDevice, c->st));
-    HCK(launch_retile(C, dst, Npad, p, 1, c->st));
+      HCK(hipMemcpy2DAsync(C, es * Npad, (const char*)A + es * j0 * lda, es * lda, es * N, nc, hipMemcpyHostToDevice,
+                           c->st));
+    HCK(launch_retile(C, in32, dst, a32, Npad, p, 1, c->st));
   }
 }
 
@@ -2191,7 +2220,7 @@ void ggn_cb_load(scs_ctx* c, const double* xh, bool sample) {
     swap_view(c, v);
     c->cbstage = dalloc<double>(c, (size_t)v.Npad * 128);
   }
-  upload_panels(c, out, n, n, v.Npad, v.A, c->cbstage);
+  upload_panels(c, out, 0, n, n, v.Npad, v.A, 0, c->cbstage);
   const double* r = out + (size_t)n * m;
   const double* q = r + n;
   if (sample) {
@@ -2252,7 +2281,7 @@ void step_newton(scs_ctx* c, const double* xh, int64_t iter, double* x_new, doub
       grad_f_dev(c, xh, c->x, c->gtmp);
     } else if (c->loss == SCS_LOSS_QUADRATIC) {
       require_dense(c, "the quadratic loss");
-      HCK(launch_half_sym(c->A, c->nstage, m, c->G, c->mpad, c->st));
+      HCK(launch_half_sym(c->A, c->nstage, m, c->G, c->mpad, c->st));   // fp64 A only (require_dense)
       grad_f_dev(c, xh, c->x, c->gtmp);
     } else {
       forward(c, xh, c->x, EPI_GRAD | EPI_HESS, false);
@@ -2414,11 +2443,11 @@ bool is_group(const scs_ctx* c);
 template <class F>
 int group_run(scs_ctx* g, F&& f);
 int group_destroy(scs_ctx* g);
-int group_set_data(scs_ctx* g, int64_t N, int64_t m, const double* A, int64_t lda, const double* y, int64_t Nglob,
-                   int64_t row0);
+int group_set_data(scs_ctx* g, int64_t N, int64_t m, const void* A, int in32, int64_t lda, const double* y,
+                   int64_t Nglob, int64_t row0);
 int group_gen_data(scs_ctx* g, const scs_synth* sp);
 int group_get_data(scs_ctx* g, int64_t r0, int64_t nr, double* A, int64_t lda_out, double* y);
-int group_set_test_data(scs_ctx* g, int64_t N, const double* A, int64_t lda, const double* y, int64_t Nglob,
+int group_set_test_data(scs_ctx* g, int64_t N, const void* A, int in32, int64_t lda, const double* y, int64_t Nglob,
                         int64_t row0);
 int group_gen_test_data(scs_ctx* g, const scs_synth* sp);
 int group_eval(scs_ctx* g, const double* x, double* out, int64_t nout, int (*fn)(scs_ctx*, const double*, double*));
@@ -2620,6 +2649,8 @@ static void reset_data(scs_ctx* c) {
     c->own_red = false;
   }
   dfree_t(c, c->A);
+  c->a32 = 0;   // the block's type goes with it; the mode (dense_f32) persists, as the solver choice does
+  if (c->prod_kname == GEMV_N_F32_NAME) c->prod_kname.clear();
   dfree_t(c, c->rowptr);
   dfree_t(c, c->colptr);
   dfree_t(c, c->colidx);
@@ -2689,22 +2720,33 @@ static void reset_data(scs_ctx* c) {
   c->reg_set = c->smooth_set = c->method_set = false;
 }
 
-int scs_set_data(scs_ctx* c, int64_t N, int64_t m, const double* A, int64_t lda, const double* y, int64_t Nglob,
-                 int64_t row0) {
-  if (is_group(c)) return group_set_data(c, N, m, A, lda, y, Nglob, row0);
+// fp32 storage does not cover the quadratic loss (its m x m A goes through launch_half_sym)
+static void refuse_f32_quadratic(scs_ctx* c, int a32) {
+  if (a32 && c->loss_set && c->loss == SCS_LOSS_QUADRATIC)
+    fail(c, SCS_ERR_ARG, "the quadratic loss needs an fp64-stored A: fp32 storage (scs_set_dense_f32 / "
+                         "scs_set_data_f32) does not cover it");
+}
+
+// scs_set_data (in32 = 0) / scs_set_data_f32 (in32 = 1: host floats, stored as they are)
+static int set_data_any(scs_ctx* c, int64_t N, int64_t m, const void* A, int in32, int64_t lda, const double* y,
+                        int64_t Nglob, int64_t row0) {
+  if (is_group(c)) return group_set_data(c, N, m, A, in32, lda, y, Nglob, row0);
   return guarded(c, [&] {
     HCK(hipSetDevice(c->dev));
+    if (A) refuse_f32_quadratic(c, in32 | c->dense_f32);
+    if (in32 && A) c->dense_f32 = 1;
     reset_data(c);
     set_dims(c, N, m, Nglob, row0);
     c->generic = (A == nullptr);
     if (!c->generic) {
       if (lda < N) fail(c, SCS_ERR_ARG, "lda (%lld) < N (%lld)", (long long)lda, (long long)N);
-      c->A = dalloc<double>(c, (size_t)c->Npad * c->mpad);
+      c->a32 = c->dense_f32;
+      c->A = alloc_A(c, c->Npad, c->a32);
       c->y = dalloc<double>(c, c->Npad);
       if (N > 0) {
         // panel by panel: host columns -> column-major staging buffer -> panel-blocked A
-        double* C = dalloc<double>(c, (size_t)c->Npad * 128);
-        upload_panels(c, A, N, lda, c->Npad, c->A, C);
+        double* C = dalloc<double>(c, (size_t)c->Npad * (in32 ? 64 : 128));   // Npad x 128 elements
+        upload_panels(c, A, in32, N, lda, c->Npad, c->A, c->a32, C);
         sync(c);
         dfree_t(c, C);
         if (y) h2d(c, c->y, y, N);
@@ -2717,22 +2759,73 @@ int scs_set_data(scs_ctx* c, int64_t N, int64_t m, const double* A, int64_t lda,
   });
 }
 
+int scs_set_data(scs_ctx* c, int64_t N, int64_t m, const double* A, int64_t lda, const double* y, int64_t Nglob,
+                 int64_t row0) {
+  return set_data_any(c, N, m, A, 0, lda, y, Nglob, row0);
+}
+
+int scs_set_data_f32(scs_ctx* c, int64_t N, int64_t m, const void* A32, int64_t lda, const double* y, int64_t Nglob,
+                     int64_t row0) {
+  if (!A32) {
+    c->err = "scs_set_data_f32: A32 is NULL (a ProblemGeneric goes through scs_set_data)";
+    return SCS_ERR_ARG;
+  }
+  return set_data_any(c, N, m, A32, 1, lda, y, Nglob, row0);
+}
+
+int scs_set_dense_f32(scs_ctx* c, int on) {
+  if (is_group(c)) return group_run(c, [&](scs_ctx* s_, int) { return scs_set_dense_f32(s_, on); });
+  return guarded(c, [&] { c->dense_f32 = on ? 1 : 0; });
+}
+
+int scs_data_info(scs_ctx* c, int* a_elem_bytes, int64_t* a_bytes, int64_t* ctx_bytes) {
+  if (is_group(c)) {   // device 0's element size, the devices' bytes summed
+    int64_t ab = 0, cb = 0;
+    for (size_t i = 0; i < c->subs.size(); ++i) {
+      int64_t a1 = 0, c1 = 0;
+      const int rc = scs_data_info(c->subs[i], i == 0 ? a_elem_bytes : nullptr, &a1, &c1);
+      if (rc != SCS_OK) {
+        c->err = c->subs[i]->err;
+        return rc;
+      }
+      ab += a1;
+      cb += c1;
+    }
+    if (a_bytes) *a_bytes = ab;
+    if (ctx_bytes) *ctx_bytes = cb;
+    return SCS_OK;
+  }
+  return guarded(c, [&] {
+    const bool dense = c->has_data && !c->generic && !c->sparse && c->A;
+    if (a_elem_bytes) *a_elem_bytes = (dense && c->a32) ? 4 : 8;
+    if (a_bytes) *a_bytes = dense ? (int64_t)a_block_bytes(c, c->Npad, c->a32) : 0;
+    if (ctx_bytes) {
+      size_t t = 0;
+      for (const DevBuf& b : c->allocs) t += b.bytes;
+      *ctx_bytes = (int64_t)t;
+    }
+  });
+}
+
 int scs_gen_data(scs_ctx* c, const scs_synth* s) {
   if (is_group(c)) return group_gen_data(c, s);
   return guarded(c, [&] {
     if (!s) fail(c, SCS_ERR_ARG, "null synth spec");
     HCK(hipSetDevice(c->dev));
+    refuse_f32_quadratic(c, c->dense_f32);
     reset_data(c);
     set_dims(c, s->N, s->m, s->N_global, s->row0);
     c->generic = false;
-    c->A = dalloc<double>(c, (size_t)c->Npad * c->mpad);
+    c->a32 = c->dense_f32;
+    c->A = alloc_A(c, c->Npad, c->a32);
     c->y = dalloc<double>(c, c->Npad);
     alloc_mspace(c);
     alloc_nspace(c);
     const double scale = (s->kind == 3) ? 1.0 : 1.0 / std::sqrt((double)s->m);
-    HCK(launch_gen_A(c->A, c->Npad, c->N, c->m, c->mpad, c->row0, s->seed, scale, c->st));
+    // fp32 mode: the rows are rounded as they are written, and y comes from the stored (rounded) rows
+    HCK(launch_gen_A(c->A, c->a32, c->Npad, c->N, c->m, c->mpad, c->row0, s->seed, scale, c->st));
     HCK(launch_gen_xtrue(c->xn, c->m, s->seed, s->density, c->st));
-    HCK(launch_gemv_n(c->A, c->nstage, c->Npad, c->mpad, c->xn, 1, c->zpart, c->Npad, c->st));
+    HCK(launch_gemv_n(c->A, c->a32, c->nstage, c->Npad, c->mpad, c->xn, 1, c->zpart, c->Npad, c->st));
     HCK(launch_gen_y(s->kind, c->zpart, c->y, c->N, c->row0, s->seed, c->st));
     sync(c);
     c->has_data = true;
@@ -2750,7 +2843,7 @@ int scs_get_data(scs_ctx* c, int64_t r0, int64_t nr, double* A, int64_t lda_out,
       for (int64_t p = 0; p < c->mpad / 128; ++p) {
         const int64_t j0 = p * 128, nc = std::min<int64_t>(128, c->m - j0);
         if (nc <= 0) break;
-        HCK(launch_retile(C, c->A, c->Npad, p, 0, c->st));
+        HCK(launch_retile(C, 0, c->A, c->a32, c->Npad, p, 0, c->st));   // fp32-stored rows come back widened
         HCK(hipMemcpy2DAsync(A + j0 * lda_out, sizeof(double) * lda_out, C + r0, sizeof(double) * c->Npad,
                              sizeof(double) * nr, nc, hipMemcpyDeviceToHost, c->st));
       }
@@ -2983,14 +3076,20 @@ static void test_view_dims(scs_ctx* c, int64_t N, int64_t Nglob, bool sparse) {
   v.nstage = v.Npad / 16;
   v.sparse = sparse;
   v.y = dalloc<double>(c, v.Npad);
-  if (!sparse) v.A = dalloc<double>(c, (size_t)v.Npad * c->mpad);
+  if (!sparse) {   // dense held-out rows follow the context's storage mode
+    v.a32 = c->dense_f32;
+    v.A = alloc_A(c, v.Npad, v.a32);
+  }
 }
 
-int scs_set_test_data(scs_ctx* c, int64_t N, const double* A, int64_t lda, const double* y, int64_t Nglob,
-                      int64_t row0) {
-  if (is_group(c)) return group_set_test_data(c, N, A, lda, y, Nglob, row0);
+// scs_set_test_data (in32 = 0) / scs_set_test_data_f32 (in32 = 1)
+static int set_test_any(scs_ctx* c, int64_t N, const void* A, int in32, int64_t lda, const double* y, int64_t Nglob,
+                        int64_t row0) {
+  if (is_group(c)) return group_set_test_data(c, N, A, in32, lda, y, Nglob, row0);
   return guarded(c, [&] {
     HCK(hipSetDevice(c->dev));
+    if (A && y) refuse_f32_quadratic(c, in32 | c->dense_f32);
+    if (in32 && A) c->dense_f32 = 1;
     free_test(c);
     if (!A && !y) return;   // clears the held-out set
     if (!A || !y) {         // the reference's xor case (iterate.jl:170-171): recorded, not an error here
@@ -3003,7 +3102,7 @@ int scs_set_test_data(scs_ctx* c, int64_t N, const double* A, int64_t lda, const
     TestScope ts(c);
     if (N > 0) {
       double* C = dalloc<double>(c, (size_t)c->Npad * 128);
-      upload_panels(c, A, N, lda, c->Npad, c->A, C);
+      upload_panels(c, A, in32, N, lda, c->Npad, c->A, c->a32, C);
       h2d(c, c->y, y, N);
       sync(c);
       dfree_t(c, C);
@@ -3012,6 +3111,16 @@ int scs_set_test_data(scs_ctx* c, int64_t N, const double* A, int64_t lda, const
     sync(c);
     c->tset.on = true;
   });
+}
+
+int scs_set_test_data(scs_ctx* c, int64_t N, const double* A, int64_t lda, const double* y, int64_t Nglob,
+                      int64_t row0) {
+  return set_test_any(c, N, A, 0, lda, y, Nglob, row0);
+}
+
+int scs_set_test_data_f32(scs_ctx* c, int64_t N, const void* A32, int64_t lda, const double* y, int64_t Nglob,
+                          int64_t row0) {
+  return set_test_any(c, N, A32, 1, lda, y, Nglob, row0);
 }
 
 int scs_set_test_sparse(scs_ctx* c, int64_t N, int64_t nnz, const int64_t* rowptr, const int32_t* colidx,
@@ -3062,6 +3171,7 @@ int scs_gen_test_data(scs_ctx* c, const scs_synth* s) {
     if (s->m != c->m) fail(c, SCS_ERR_ARG, "scs_gen_test_data: m = %lld, the data has %lld", (long long)s->m,
                            (long long)c->m);
     HCK(hipSetDevice(c->dev));
+    refuse_f32_quadratic(c, c->dense_f32);
     free_test(c);
     test_view_dims(c, s->N, s->N_global, false);
     TestScope ts(c);
@@ -3069,9 +3179,9 @@ int scs_gen_test_data(scs_ctx* c, const scs_synth* s) {
     const double scale = (s->kind == 3) ? 1.0 : 1.0 / std::sqrt((double)s->m);
     // rows [row0, row0 + N) of the same generator as scs_gen_data: with row0 >= the data's N_global
     // they are held-out samples of the same distribution (the same x_true)
-    HCK(launch_gen_A(c->A, c->Npad, c->N, c->m, c->mpad, s->row0, s->seed, scale, c->st));
+    HCK(launch_gen_A(c->A, c->a32, c->Npad, c->N, c->m, c->mpad, s->row0, s->seed, scale, c->st));
     HCK(launch_gen_xtrue(c->xn, c->m, s->seed, s->density, c->st));
-    HCK(launch_gemv_n(c->A, c->nstage, c->Npad, c->mpad, c->xn, 1, c->zpart, c->Npad, c->st));
+    HCK(launch_gemv_n(c->A, c->a32, c->nstage, c->Npad, c->mpad, c->xn, 1, c->zpart, c->Npad, c->st));
     HCK(launch_gen_y(s->kind, c->zpart, c->y, c->N, s->row0, s->seed, c->st));
     sync(c);
     c->tset.on = true;
@@ -3121,6 +3231,9 @@ int scs_set_loss(scs_ctx* c, int loss, int ggn, double scale) {
       fail(c, SCS_ERR_ARG, "a callback loss holds no device data: scs_set_data(N = 0, A = NULL, m) first");
     if (loss == SCS_LOSS_CALLBACK && ggn != SCS_GGN_NONE)
       fail(c, SCS_ERR_ARG, "a callback loss has no out_fn kind (its GGN pieces come from the callback)");
+    if (loss == SCS_LOSS_QUADRATIC && ((c->has_data && !c->generic && !c->sparse && c->a32) || c->tset.v.a32))
+      fail(c, SCS_ERR_ARG, "the quadratic loss needs an fp64-stored A: fp32 storage (scs_set_dense_f32 / "
+                           "scs_set_data_f32) does not cover it");
     c->loss = loss;
     c->ggn = ggn;
     c->scale = scale;
@@ -4111,7 +4224,7 @@ int scs_get_columns(scs_ctx* c, const int64_t* cols, int64_t ncols, double* out)
     int64_t* dc = dalloc<int64_t>(c, ncols);
     double* dout = dalloc<double>(c, (size_t)ncols * c->N);
     HCK(hipMemcpyAsync(dc, cols, sizeof(int64_t) * ncols, hipMemcpyHostToDevice, c->st));
-    HCK(launch_get_columns(c->A, c->nstage, dc, ncols, c->N, dout, c->st));
+    HCK(launch_get_columns(c->A, c->a32, c->nstage, dc, ncols, c->N, dout, c->st));
     HCK(hipMemcpyAsync(out, dout, sizeof(double) * ncols * c->N, hipMemcpyDeviceToHost, c->st));
     sync(c);
     dfree_t(c, dc);
@@ -4568,9 +4681,10 @@ int group_destroy(scs_ctx* g) {
   return SCS_OK;
 }
 
-int group_set_data(scs_ctx* g, int64_t N, int64_t m, const double* A, int64_t lda, const double* y, int64_t Nglob,
-                   int64_t row0) {
+int group_set_data(scs_ctx* g, int64_t N, int64_t m, const void* A, int in32, int64_t lda, const double* y,
+                   int64_t Nglob, int64_t row0) {
   const int n = (int)g->subs.size();
+  const size_t es = in32 ? sizeof(float) : sizeof(double);
   if ((Nglob > 0 && Nglob != N) || row0 != 0) {
     g->err = "a multi-device context holds the whole problem: N_global = N, row0 = 0 (it splits the rows itself)";
     return SCS_ERR_ARG;
@@ -4582,8 +4696,8 @@ int group_set_data(scs_ctx* g, int64_t N, int64_t m, const double* A, int64_t ld
   g->plan = A ? row_plan(N, n) : std::vector<RowBlock>((size_t)n);
   const int rc = group_run(g, [&](scs_ctx* s, int i) {
     const RowBlock b = g->plan[(size_t)i];
-    return scs_set_data(s, A ? b.rows() : 0, m, A ? A + b.r0 : nullptr, lda, y ? y + b.r0 : nullptr, A ? N : 0,
-                        b.r0);
+    return set_data_any(s, A ? b.rows() : 0, m, A ? (const char*)A + es * b.r0 : nullptr, in32, lda,
+                        y ? y + b.r0 : nullptr, A ? N : 0, b.r0);
   });
   if (rc == SCS_OK) {
     g->grpN = A ? N : 0;
@@ -4629,8 +4743,9 @@ int group_get_data(scs_ctx* g, int64_t r0, int64_t nr, double* A, int64_t lda_ou
 }
 
 // the held-out rows split like the data's (row_plan; a device may hold none of them)
-int group_set_test_data(scs_ctx* g, int64_t N, const double* A, int64_t lda, const double* y, int64_t Nglob,
+int group_set_test_data(scs_ctx* g, int64_t N, const void* A, int in32, int64_t lda, const double* y, int64_t Nglob,
                         int64_t row0) {
+  const size_t es = in32 ? sizeof(float) : sizeof(double);
   if ((Nglob > 0 && Nglob != N) || row0 != 0) {
     g->err = "a multi-device context holds the whole test set: N_global = N, row0 = 0";
     return SCS_ERR_ARG;
@@ -4638,7 +4753,8 @@ int group_set_test_data(scs_ctx* g, int64_t N, const double* A, int64_t lda, con
   const std::vector<RowBlock> plan = row_plan(std::max<int64_t>(N, 0), (int)g->subs.size());
   return group_run(g, [&](scs_ctx* s, int i) {
     const RowBlock b = plan[(size_t)i];
-    return scs_set_test_data(s, b.rows(), A ? A + b.r0 : nullptr, lda, y ? y + b.r0 : nullptr, N, b.r0);
+    return set_test_any(s, b.rows(), A ? (const char*)A + es * b.r0 : nullptr, in32, lda, y ? y + b.r0 : nullptr, N,
+                        b.r0);
   });
 }
 

@@ -15,7 +15,7 @@ using SelfConcordantSmoothOptimization
 import SelfConcordantSmoothOptimization: step!, init!, ProximalMethod, ProxModel, is_interval_set
 
 export DeviceProblem, configure!, iterate_device!, set_gram_cache!, set_solver!, rccl_unique_id, set_comm_rccl!,
-       set_comm_callback!, set_test!, set_compute_f32!, fallback_counts
+       set_comm_callback!, set_test!, set_compute_f32!, fallback_counts, data_info
 
 const lib = joinpath(@__DIR__, "..", "scsopt", "libscsopt.so")
 
@@ -127,6 +127,10 @@ function set_test!(model::DeviceProblem, Atest, ytest; Ntest_global::Integer=0, 
                   (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Int32}, Ptr{Float64}, Cint, Ptr{Float64}, Int64, Int64),
                   ctx, size(Atest, 1), nnz(Atest), rowptr, colidx, val, val_f32 ? 1 : 0, yt, Ntest_global,
                   test_row0), ctx)
+    elseif Atest isa Matrix{Float32}                          # stored as fp32 on the device, as it is
+        chk(ccall((:scs_set_test_data_f32, lib), Cint,
+                  (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Int64),
+                  ctx, size(Atest, 1), Atest, size(Atest, 1), yt, Ntest_global, test_row0), ctx)
     else
         Am = Matrix{Float64}(Atest)
         chk(ccall((:scs_set_test_data, lib), Cint,
@@ -154,6 +158,34 @@ function DeviceProblem(A::Matrix{Float64}, y::AbstractVector, x0::Vector{Float64
               ctx, N, m, A, N, yv, N_global, row0), ctx)
     model = finish_problem(ctx, A, yv, x0, loss, λ, out_fn, scale, L, sol, C_set, P)
     return set_test!(model, Atest, ytest; Ntest_global, test_row0)
+end
+
+# A::Matrix{Float32} (A::DataTupleOrArray2 admits it, problems.jl:61-62; with x::Vector{Float64} Julia
+# promotes every product to Float64): the rows are stored as fp32 on the device as they are -- half
+# the memory of A, fp64 arithmetic, bit for bit what Float64.(A) gives (scs_set_data_f32).  An
+# Atest::Matrix{Float32} is stored the same way; any other dense Atest is rounded to fp32 on the device.
+function DeviceProblem(A::Matrix{Float32}, y::AbstractVector, x0::Vector{Float64}, loss::Symbol, λ;
+                       out_fn::Union{Symbol,Nothing}=nothing, scale::Float64=1.0 / size(A, 1),
+                       L=nothing, sol::Vector{Float64}=zero(x0), C_set=nothing, P=nothing, device::Integer=0,
+                       N_global::Integer=size(A, 1), row0::Integer=0, devices=nothing,
+                       device_exchange::Symbol=:rccl, Atest=nothing,
+                       ytest=nothing, Ntest_global::Integer=0, test_row0::Integer=0)
+    ctx = create_ctx(device, devices, device_exchange)
+    N, m = size(A)
+    yv = Vector{Float64}(y)
+    chk(ccall((:scs_set_data_f32, lib), Cint,
+              (Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Int64),
+              ctx, N, m, A, N, yv, N_global, row0), ctx)
+    model = finish_problem(ctx, A, yv, x0, loss, λ, out_fn, scale, L, sol, C_set, P)
+    return set_test!(model, Atest, ytest; Ntest_global, test_row0)
+end
+
+# (element bytes of the dense A: 8 or 4, bytes of that block, device bytes the context holds)
+function data_info(model::DeviceProblem)
+    eb = Ref{Cint}(0); ab = Ref{Int64}(0); cb = Ref{Int64}(0)
+    chk(ccall((:scs_data_info, lib), Cint, (Ptr{Cvoid}, Ref{Cint}, Ref{Int64}, Ref{Int64}), model.ctx, eb, ab, cb),
+        model.ctx)
+    return Int(eb[]), ab[], cb[]
 end
 
 # A::SparseMatrixCSC (README.md:105 builds it with sprandn): its CSC arrays are the column copy;

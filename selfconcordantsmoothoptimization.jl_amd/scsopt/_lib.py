@@ -109,9 +109,14 @@ _SIGS = {
                                 C.POINTER(C.c_int), C.c_char_p, C.c_int64]),
     "scs_set_data": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, c_dp, C.c_int64, c_dp, C.c_int64, C.c_int64]),
     "scs_gen_data": (C.c_int, [C.c_void_p, C.POINTER(Synth)]),
+    "scs_set_dense_f32": (C.c_int, [C.c_void_p, C.c_int]),
+    "scs_set_data_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, c_dp, C.c_int64,
+                                   C.c_int64]),
+    "scs_data_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), c_i64p, c_i64p]),
     "scs_get_data": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, c_dp, C.c_int64, c_dp]),
     "scs_get_dims": (C.c_int, [C.c_void_p, c_i64p, c_i64p, c_i64p, c_i64p]),
     "scs_set_test_data": (C.c_int, [C.c_void_p, C.c_int64, c_dp, C.c_int64, c_dp, C.c_int64, C.c_int64]),
+    "scs_set_test_data_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, c_dp, C.c_int64, C.c_int64]),
     "scs_set_test_sparse": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, c_i64p, c_i32p, c_dp, C.c_int, c_dp,
                                       C.c_int64, C.c_int64]),
     "scs_gen_test_data": (C.c_int, [C.c_void_p, C.POINTER(Synth)]),

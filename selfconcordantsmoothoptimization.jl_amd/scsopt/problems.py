@@ -86,7 +86,7 @@ class Problem:
     def __init__(self, *args, Atest=None, ytest=None, L=None, sol=None, C_set=None, P=None,
                  out_fn: Optional[OutFn] = None, name=None, device=0, comm=None, N_global=None, row0=0,
                  sparse_f32=False, devices=None, device_exchange="rccl", Ntest_global=None, test_row0=0,
-                 _ctx=None):
+                 dense_f32=False, _ctx=None):
         if len(args) == 5:
             A, y, x0, f, lam = args
         elif len(args) == 3:
@@ -117,6 +117,9 @@ class Problem:
         if devices is not None and (comm is not None or _is_sparse(A)):
             raise ValueError("devices=[...] (one process, several GPUs) takes a dense A and no comm")
         self.ctx = _ctx if _ctx is not None else _lib.Context(device, devices=devices, device_exchange=device_exchange)
+        # dense_f32: a dense A (and dense held-out rows) stored as fp32 on the device, fp64 arithmetic --
+        # bit for bit what the same values widened to fp64 give (scs_set_dense_f32)
+        self.dense_f32 = bool(dense_f32)
         if comm is not None and comm.active and _ctx is None:
             comm.attach(self.ctx)
         if _ctx is None:
@@ -126,16 +129,24 @@ class Problem:
             elif _is_sparse(A):
                 self._set_sparse(A, y, N_global, row0, f32=bool(sparse_f32))
             else:
-                A = np.asarray(A, dtype=np.float64)
+                # a float32 matrix goes to the device as it is only with dense_f32; the default widens it
+                as32 = self.dense_f32 and isinstance(A, np.ndarray) and A.dtype == np.float32
+                A = np.asarray(A, dtype=np.float32 if as32 else np.float64)
                 if A.ndim != 2 or A.shape[1] != self.m:
                     raise ValueError(f"A must be N x m with m = length(x0) = {self.m}")
                 Af = np.asfortranarray(A)  # Julia layout: column-major, lda = N
                 yv = np.ascontiguousarray(np.asarray(y, dtype=np.float64).reshape(-1))
                 self.N = int(A.shape[0])
                 Ng = self.N if N_global is None else int(N_global)
-                self.ctx.check(_lib.lib.scs_set_data(self.ctx.h, self.N, self.m,
-                                                     Af.ctypes.data_as(_lib.c_dp), self.N, dptr(yv), Ng,
-                                                     int(row0)))
+                if as32:
+                    self.ctx.check(_lib.lib.scs_set_data_f32(self.ctx.h, self.N, self.m, Af.ctypes.data_as(C.c_void_p),
+                                                             self.N, dptr(yv), Ng, int(row0)))
+                else:
+                    if self.dense_f32:   # fp64 (or any other) input: rounded to fp32 on the device
+                        self.ctx.check(_lib.lib.scs_set_dense_f32(self.ctx.h, 1))
+                    self.ctx.check(_lib.lib.scs_set_data(self.ctx.h, self.N, self.m,
+                                                         Af.ctypes.data_as(_lib.c_dp), self.N, dptr(yv), Ng,
+                                                         int(row0)))
         else:
             N = C.c_int64()
             self.ctx.check(_lib.lib.scs_get_dims(self.ctx.h, C.byref(N), None, None, None))
@@ -207,12 +218,19 @@ class Problem:
                 self.ctx.h, int(csr.shape[0]), int(val.shape[0]), rowptr.ctypes.data_as(_lib.c_i64p),
                 colidx.ctypes.data_as(_lib.c_i32p), dptr(val), 1 if sparse_f32 else 0, dptr(yv), Ng, int(row0)))
         else:
-            At = np.asarray(Atest, dtype=np.float64)
+            # the held-out rows follow the context's storage mode (float32 rows as they are with dense_f32)
+            as32 = self.dense_f32 and isinstance(Atest, np.ndarray) and Atest.dtype == np.float32
+            At = np.asarray(Atest, dtype=np.float32 if as32 else np.float64)
             if At.ndim != 2 or At.shape[1] != self.m or At.shape[0] != yv.shape[0]:
                 raise ValueError(f"Atest must be Ntest x m (m = {self.m}) with len(ytest) = Ntest")
             Af = np.asfortranarray(At)
-            self.ctx.check(_lib.lib.scs_set_test_data(self.ctx.h, int(At.shape[0]), Af.ctypes.data_as(_lib.c_dp),
-                                                      int(At.shape[0]), dptr(yv), Ng, int(row0)))
+            if as32:
+                self.ctx.check(_lib.lib.scs_set_test_data_f32(self.ctx.h, int(At.shape[0]),
+                                                              Af.ctypes.data_as(C.c_void_p), int(At.shape[0]),
+                                                              dptr(yv), Ng, int(row0)))
+            else:
+                self.ctx.check(_lib.lib.scs_set_test_data(self.ctx.h, int(At.shape[0]), Af.ctypes.data_as(_lib.c_dp),
+                                                          int(At.shape[0]), dptr(yv), Ng, int(row0)))
         self.test_model = True
 
     def gen_test(self, Ntest, *, row0=None, seed=1234, kind=1, density=0.1):
@@ -316,11 +334,12 @@ class Problem:
 
     @classmethod
     def synthetic(cls, N, m, x0, f, lam, *, kind=1, seed=1234, density=0.1, out_fn=None, device=0,
-                  comm=None, devices=None, device_exchange="rccl", test_N=None, **kw):
+                  comm=None, devices=None, device_exchange="rccl", test_N=None, dense_f32=False, **kw):
         """A ~ N(0,1)/sqrt(m) (kind 1, 2) or N(0,1) (kind 3) generated on the device, y from a
         sparse x_true (kind 1: Bernoulli(σ(A x_true)) ∈ {0,1}; kind 2: ±1; kind 3: A x_true + 0.1ε).
         With comm, this rank generates its contiguous row shard in place; with devices=[...] one
-        process drives those GPUs and the library generates each one's row block."""
+        process drives those GPUs and the library generates each one's row block.  dense_f32: the
+        rows are stored rounded to fp32 and y is formed from the stored rows."""
         from .shard import row_range
         if devices is not None and comm is not None:
             raise ValueError("devices=[...] (one process, several GPUs) and comm (one process per GPU) exclude "
@@ -331,8 +350,10 @@ class Problem:
         if comm is not None and comm.active:
             comm.attach(ctx)
         spec = _lib.Synth(N_global=N, row0=r0, N=r1 - r0, m=m, seed=seed, kind=kind, density=density)
+        if dense_f32:
+            ctx.check(_lib.lib.scs_set_dense_f32(ctx.h, 1))
         ctx.check(_lib.lib.scs_gen_data(ctx.h, C.byref(spec)))
-        p = cls(x0, f, lam, out_fn=out_fn, device=device, comm=comm, _ctx=ctx, **kw)
+        p = cls(x0, f, lam, out_fn=out_fn, device=device, comm=comm, dense_f32=dense_f32, _ctx=ctx, **kw)
         if test_N:   # held-out rows [N, N + test_N) of the same generator (same x_true)
             p.gen_test(int(test_N), row0=N, seed=seed, kind=kind, density=density)
         return p
@@ -407,6 +428,13 @@ class Problem:
         y = np.zeros(nr, dtype=np.float64)
         self.ctx.check(_lib.lib.scs_get_data(self.ctx.h, r0, nr, dptr(A), nr, dptr(y)))
         return np.ascontiguousarray(A.T), y
+
+    def data_info(self):
+        """(element bytes of the dense A: 8 or 4, bytes of that block, device bytes the context holds)
+        -- scs_data_info."""
+        eb, ab, cb = C.c_int(), C.c_int64(), C.c_int64()
+        self.ctx.check(_lib.lib.scs_data_info(self.ctx.h, C.byref(eb), C.byref(ab), C.byref(cb)))
+        return int(eb.value), int(ab.value), int(cb.value)
 
     def configure(self, reg_name, hmu: Smoother):
         """Push reg_name / λ / C_set / P and the smoother to the device context."""

@@ -11,7 +11,7 @@
 namespace scs {
 void gram_tile_list(int nb, int2* out, int* ntiles);
 void gram_tile_list_tall(int nb, int2* out, int* ntiles);
-hipError_t gram_launch(const double* A, int64_t S, const double* w, int64_t Nk, const int2* tiles, int ntiles,
+hipError_t gram_launch(const void* A, int a32, int64_t S, const double* w, int64_t Nk, const int2* tiles, int ntiles,
                        double* G, int64_t ldg, int packed, int tall, hipStream_t st, const double* v = nullptr,
                        double* VP = nullptr, int64_t vps = 0);
 hipError_t gram_launch_ex(const double* A, int64_t lda, const double* w, int64_t k0, int64_t k1, const int2* tiles,
@@ -52,7 +52,7 @@ static int run(int64_t N, int64_t m, int reps, bool check, int tall) {
   CK(hipMalloc(&dtl, nt * sizeof(int2)));
   CK(hipMemcpy(dtl, tl.data(), nt * sizeof(int2), hipMemcpyHostToDevice));
   // gram_launch reads the panel-blocked layout (S = N/16 stages); the fill is layout-agnostic
-  CK(scs::gram_launch(A, N / 16, w, N, dtl, nt, G, m, 0, tall, 0));
+  CK(scs::gram_launch(A, 0, N / 16, w, N, dtl, nt, G, m, 0, tall, 0));
   CK(hipDeviceSynchronize());
   if (check) {
     std::vector<double> hA((size_t)lda * m), hw(N), hG((size_t)m * m);
@@ -144,7 +144,7 @@ static int run(int64_t N, int64_t m, int reps, bool check, int tall) {
     }
   }
   CK(hipEventRecord(e0));
-  for (int r = 0; r < reps; ++r) CK(scs::gram_launch(A, N / 16, w, N, dtl, nt, G, m, 0, tall, 0));
+  for (int r = 0; r < reps; ++r) CK(scs::gram_launch(A, 0, N / 16, w, N, dtl, nt, G, m, 0, tall, 0));
   CK(hipEventRecord(e1));
   CK(hipEventSynchronize(e1));
   float ms;
