@@ -240,7 +240,32 @@ int scs_set_data_f32(scs_ctx* ctx, int64_t N, int64_t m, const void* A32, int64_
  * (0 without one); ctx_bytes: device bytes the context holds now, summed over its own allocations
  * (a multi-device context: device 0's element size, bytes summed).  Any pointer may be NULL.    */
 int scs_data_info(scs_ctx* ctx, int* a_elem_bytes, int64_t* a_bytes, int64_t* ctx_bytes);
-/* ---- held-out data  (Problem(A, y, x0, f, λ; Atest, ytest), problems.jl:27-28,67-68) -------
+/* ---- a dense A that is already on the device  (a torch-ROCm tensor, a CuPy array, a ROCArray) ---
+ * dA is device memory on the context's device (checked with hipPointerGetAttributes before anything
+ * is launched; anything else is refused with SCS_ERR_ARG).  Element (n, j) of the N x m matrix sits
+ * at dA[n*stride_n + j*stride_m], elements of elem_bytes = 8 (double) or 4 (float).  Strides are in
+ * elements and one of them must be 1: stride_m = 1 with stride_n >= m is a row-major matrix (the
+ * NumPy / torch default, or a column slice of a wider one), stride_n = 1 with stride_m >= N a
+ * column-major one.  One kernel pass re-tiles the matrix into the panel-blocked block on the
+ * context's stream, zero padding included: no staging buffer, no host copy, no memset.  Peak device
+ * memory is the source plus the tiled block.
+ * The stored type is the context's mode alone (scs_set_dense_f32): unlike scs_set_data_f32 an fp32
+ * source does not switch it on, and all four source x storage pairs are legal (a double source into
+ * fp32 storage is rounded to nearest even, a float source into fp64 storage widened).  The stored
+ * block is bit for bit what scs_set_data / scs_set_data_f32 store from the same values.
+ * y (N doubles) may be a host or a device pointer; the library asks the pointer's attributes.
+ * src_stream: the stream the producer of dA (and of a device y) ran on; the context's stream waits
+ * for the work already queued on it (event record + wait).  NULL: the caller guarantees the source is
+ * complete.  The two values of __cuda_array_interface__ are taken as well: (void*)1, the legacy default
+ * stream (the event is recorded on the NULL stream), and (void*)2, the per-thread default stream (the
+ * library synchronises the device instead); neither is handed to the runtime as a handle.  The call returns after the context's stream is synchronised, so the source may be freed
+ * on return.  N_global / row0 describe the shard as in scs_set_data.  Refused with SCS_ERR_ARG:
+ * elem_bytes other than 4 or 8, two non-unit strides, a stride smaller than the extent it spans, a
+ * NULL dA, and a multi-device context (scs_create_multi*: it would have to split the device array). */
+int scs_set_data_device(scs_ctx* ctx, int64_t N, int64_t m, const void* dA, int elem_bytes,
+                        int64_t stride_n, int64_t stride_m, const double* y, void* src_stream,
+                        int64_t N_global, int64_t row0);
+/* ---- held-out data (Problem(A, y, x0, f, λ; Atest, ytest), problems.jl:27-28,67-68) -------
  * optim_loop! evaluates ftest(x) = f(Atest, ytest, x) with the problem's own f (same loss kind,
  * same scale literal) at every stats push when BOTH Atest and ytest are given (iterate.jl:169-175,
  * utils.jl:55-57); the values become Solution.fvaltest (scs_history.fvaltest).  Call after the
@@ -256,6 +281,11 @@ int scs_set_test_data(scs_ctx* ctx, int64_t N, const double* A, int64_t lda, con
  * storage mode on (scs_set_dense_f32).  Dense held-out rows of an fp32-mode context are fp32.   */
 int scs_set_test_data_f32(scs_ctx* ctx, int64_t N, const void* A32, int64_t lda, const double* y,
                           int64_t N_global, int64_t row0);
+/* The same from a device matrix (N x the data's m), as scs_set_data_device takes it; dA and y are
+ * both required.                                                                               */
+int scs_set_test_data_device(scs_ctx* ctx, int64_t N, const void* dA, int elem_bytes,
+                             int64_t stride_n, int64_t stride_m, const double* y, void* src_stream,
+                             int64_t N_global, int64_t row0);
 /* CSR held-out rows (0-based, m columns; values stored fp64, or fp32 with val_f32 = 1).       */
 int scs_set_test_sparse(scs_ctx* ctx, int64_t N, int64_t nnz, const int64_t* rowptr, const int32_t* colidx,
                         const double* val, int val_f32, const double* y, int64_t N_global, int64_t row0);

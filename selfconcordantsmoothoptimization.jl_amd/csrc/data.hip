@@ -292,6 +292,173 @@ hipError_t launch_retile(void* C, int c32, void* A, int a32, int64_t Npad, int64
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// A strided DEVICE matrix -> the panel-blocked A (scs_set_data_device): element (n, j) of the source
+// at src[n*stride_n + j*stride_m], TS = double | float; TD = the stored type.  One workgroup per
+// destination block (panel p, stage s: [128 features][16 samples] of TD, contiguous); every element
+// of the block is written exactly once, rows n >= N and features j >= m as zeros, so the block needs
+// no memset.  Conversions are plain casts, as in retile_kernel (double -> float rounds to nearest
+// even, float -> double is exact).  All offsets are 64-bit.
+//
+// `vec`: the host found the source base and the leading stride aligned for wide loads; otherwise
+// (a view that starts at an odd element, an odd leading stride) every element is loaded on its own.
+// Both paths fill the same registers / LDS image, so they store the same bits.
+// ---------------------------------------------------------------------------
+typedef float v4f __attribute__((ext_vector_type(4)));
+template <typename T> struct vec16;   // 16 bytes of T
+template <> struct vec16<double> { typedef v2d type; };
+template <> struct vec16<float> { typedef v4f type; };
+
+// Row-major source (stride_m == 1): the block's source is 16 rows of 128 contiguous features.
+//   LDS image   tile[16 samples][DT_PITCH] of TS (the SOURCE type: the cast sits on the way out), the
+//               128 features of a sample contiguous, DT_PITCH = 132 elements (a 16-B multiple per row).
+//   load side   thread t takes one 16-B vector (ES = 2 doubles | 4 floats) per pass: sample
+//               k*RPP + t / LPR, features (t % LPR)*ES ..; LPR = 128 / ES lanes cover a row, so a
+//               wave reads 1 KiB of one row (double) or 512 B of two (float).  The ds_write_b128 is
+//               served 8 consecutive lanes at a time: 128 contiguous bytes of one row, all 32 banks
+//               once, whatever the pitch.
+//   store side  wave w of pass k owns 1 KiB of the block: FW = 8 (TD double) | 16 (TD float) features
+//               x 16 samples.  Lane l takes feature f0 + l % FW and the ED = 2 | 4 samples
+//               (l / FW)*ED ..: ED scalar LDS reads (ds_read_b64 | ds_read_b32, served 32 lanes at a
+//               time over 32 slots of the element size), one 16-B global store; the wave's 64 stores
+//               tile its 1 KiB.  Read i of lanes 0..31 hits slot ((l/FW)*ED + i)*132 + l % FW + f0:
+//               TD double: 2*132 = 8 (mod 32), l/FW = 0..3, l % FW = 0..7  -> 32 different slots;
+//               TD float : 4*132 = 16 (mod 32), l/FW = 0..1, l % FW = 0..15 -> 32 different slots;
+//               lanes 32..63 likewise.  (The compiler pairs the reads into ds_read2_b32 /
+//               ds_read2[st64]_b64; the 8-byte form is served 16 lanes at a time over the 32 four-byte
+//               banks, where the same arithmetic gives 16 different even banks.)  Neither side has a
+//               bank conflict.
+// Blocks are numbered panel-fastest, so the workgroups in flight read whole source rows.
+constexpr int DT_PITCH = 132;
+
+template <typename TS, typename TD>
+__global__ __launch_bounds__(256) void tile_rows_kernel(const TS* __restrict__ src, int64_t stride_n, int64_t N,
+                                                        int64_t m, int64_t S, int64_t np, TD* __restrict__ A,
+                                                        int vec) {
+  typedef typename vec16<TS>::type VS;
+  typedef typename vec16<TD>::type VD;
+  constexpr int ES = 16 / sizeof(TS), ED = 16 / sizeof(TD);
+  constexpr int LPR = 128 / ES, RPP = 256 / LPR, NLD = 16 / RPP;   // lanes per row, rows per pass, passes
+  constexpr int FW = 4 * ED, NST = 128 / (4 * FW);                 // features per wave store, store passes
+  __shared__ __attribute__((aligned(16))) TS tile[16 * DT_PITCH];
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int64_t total = S * np;
+  for (int64_t b = blockIdx.x; b < total; b += gridDim.x) {
+    const int64_t s = b / np, p = b - s * np;
+    const int64_t n0 = s * 16, j0 = p * 128;
+    if (vec) {
+      VS r[NLD];
+#pragma unroll
+      for (int k = 0; k < NLD; ++k) {
+        const int64_t n = n0 + k * RPP + t / LPR, j = j0 + (t % LPR) * ES;
+        VS v = (VS)(TS)0;
+        if (n < N) {
+          const TS* q = src + n * stride_n + j;
+          if (j + ES <= m) v = *(const VS*)q;
+          else {
+#pragma unroll
+            for (int i = 0; i < ES; ++i)
+              if (j + i < m) v[i] = q[i];
+          }
+        }
+        r[k] = v;
+      }
+#pragma unroll
+      for (int k = 0; k < NLD; ++k) *(VS*)&tile[(k * RPP + t / LPR) * DT_PITCH + (t % LPR) * ES] = r[k];
+    } else {
+      TS r[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {   // element k*256 + t of the 16 x 128 source piece, row by row
+        const int64_t n = n0 + 2 * k + (t >> 7), j = j0 + (t & 127);
+        r[k] = (n < N && j < m) ? src[n * stride_n + j] : (TS)0;
+      }
+#pragma unroll
+      for (int k = 0; k < 8; ++k) tile[(2 * k + (t >> 7)) * DT_PITCH + (t & 127)] = r[k];
+    }
+    __syncthreads();
+    TD* blk = A + (p * S + s) * (128 * 16);
+#pragma unroll
+    for (int k = 0; k < NST; ++k) {
+      const int f = (k * 4 + w) * FW + lane % FW, nn = (lane / FW) * ED;
+      VD o;
+#pragma unroll
+      for (int i = 0; i < ED; ++i) o[i] = (TD)tile[(nn + i) * DT_PITCH + f];
+      *(VD*)(blk + f * 16 + nn) = o;
+    }
+    __syncthreads();   // the next block's loads overwrite the image
+  }
+}
+
+// Column-major source (stride_n == 1): feature j offers the 16 samples of a stage as one contiguous
+// piece (128 B of doubles, 64 B of floats), which is the destination's own order; no LDS.  The walk is
+// retile_kernel's: thread t of pass k writes the 16-B vector k*256 + t of the block, ED = 2 | 4
+// consecutive samples of one feature, from ED consecutive source elements (one 8-, 16- or 32-B load
+// when `vec`).  Blocks are numbered stage-fastest: source and destination both advance contiguously.
+template <typename TS, typename TD>
+__global__ __launch_bounds__(256) void tile_cols_kernel(const TS* __restrict__ src, int64_t stride_m, int64_t N,
+                                                        int64_t m, int64_t S, int64_t np, TD* __restrict__ A,
+                                                        int vec) {
+  typedef typename vec16<TD>::type VD;
+  constexpr int ED = 16 / sizeof(TD);
+  constexpr int AL = (ED * sizeof(TS) < 16) ? ED * sizeof(TS) : 16;   // what `vec` promises
+  typedef TS VS __attribute__((ext_vector_type(ED)));
+  const int t = threadIdx.x;
+  const int64_t total = S * np;
+  for (int64_t b = blockIdx.x; b < total; b += gridDim.x) {
+    const int64_t p = b / S, s = b - p * S;
+    TD* blk = A + b * (128 * 16);
+#pragma unroll
+    for (int k = 0; k < 2048 / ED / 256; ++k) {
+      const int e = (k * 256 + t) * ED;
+      const int64_t n = s * 16 + (e & 15), j = p * 128 + (e >> 4);
+      VD o = (VD)(TD)0;
+      if (j < m && n < N) {
+        const TS* q = src + j * stride_m + n;
+        if (vec && n + ED <= N) {
+          VS v;
+          __builtin_memcpy(&v, __builtin_assume_aligned(q, AL), sizeof(VS));
+          o = __builtin_convertvector(v, VD);
+        } else {
+#pragma unroll
+          for (int i = 0; i < ED; ++i)
+            if (n + i < N) o[i] = (TD)q[i];
+        }
+      }
+      *(VD*)(blk + e) = o;
+    }
+  }
+}
+
+template <typename TS, typename TD>
+static hipError_t launch_tile_device_t(const TS* src, int64_t stride_n, int64_t stride_m, int64_t N, int64_t m,
+                                       int64_t Npad, int64_t mpad, TD* A, hipStream_t st) {
+  const int64_t S = Npad / 16, np = mpad / 128;
+  const unsigned grid = (unsigned)std::min<int64_t>(S * np, 0x7fffffff);
+  const uintptr_t base = (uintptr_t)src;
+  if (stride_m == 1 && (stride_n != 1 || N <= 1)) {
+    const int vec = base % 16 == 0 && (stride_n * (int64_t)sizeof(TS)) % 16 == 0;
+    hipLaunchKernelGGL((tile_rows_kernel<TS, TD>), dim3(grid), dim3(256), 0, st, src, stride_n, N, m, S, np, A, vec);
+  } else {
+    constexpr int64_t ED = 16 / sizeof(TD);
+    constexpr int64_t AL = (ED * sizeof(TS) < 16) ? ED * sizeof(TS) : 16;
+    const int vec = base % AL == 0 && (stride_m * (int64_t)sizeof(TS)) % AL == 0;
+    hipLaunchKernelGGL((tile_cols_kernel<TS, TD>), dim3(grid), dim3(256), 0, st, src, stride_m, N, m, S, np, A, vec);
+  }
+  return hipGetLastError();
+}
+
+// src: N x m device matrix, s32: float elements; one of the strides is 1 (the caller checked them
+// and the pointer); A: Npad x mpad panel-blocked, a32: float elements
+hipError_t launch_tile_device(const void* src, int s32, int64_t stride_n, int64_t stride_m, int64_t N, int64_t m,
+                              int64_t Npad, int64_t mpad, void* A, int a32, hipStream_t st) {
+  if (stride_n != 1 && stride_m != 1) return hipErrorInvalidValue;
+  if (s32 && a32)
+    return launch_tile_device_t((const float*)src, stride_n, stride_m, N, m, Npad, mpad, (float*)A, st);
+  if (s32) return launch_tile_device_t((const float*)src, stride_n, stride_m, N, m, Npad, mpad, (double*)A, st);
+  if (a32) return launch_tile_device_t((const double*)src, stride_n, stride_m, N, m, Npad, mpad, (float*)A, st);
+  return launch_tile_device_t((const double*)src, stride_n, stride_m, N, m, Npad, mpad, (double*)A, st);
+}
+
 __global__ void ls_pair_kernel(const double* __restrict__ z0, const double* __restrict__ zd, double alpha,
                                int64_t Npad, double* __restrict__ out) {
   for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < Npad; n += (int64_t)gridDim.x * blockDim.x) {

@@ -367,6 +367,8 @@ hipError_t launch_gemv_t(const void* A, int a32, int64_t S, int64_t Npad, int64_
 // panel p: column-major Npad x 128 buffer C <-> tiled A (to_tiled = 1: C -> A; a double C into a float A
 // rounds to nearest even; c32: C holds floats, a32 only)
 hipError_t launch_retile(void* C, int c32, void* A, int a32, int64_t Npad, int64_t p, int to_tiled, hipStream_t st);
+hipError_t launch_tile_device(const void* src, int s32, int64_t stride_n, int64_t stride_m, int64_t N, int64_t m,
+                              int64_t Npad, int64_t mpad, void* A, int a32, hipStream_t st);
 // out[j] = Σ_chunk part[chunk][j] (+ lam*add[j] if add)
 hipError_t launch_gemv_t_finalize(const double* part, int nchunk, int64_t mpad, int64_t m, double* out,
                                   hipStream_t st);

@@ -425,13 +425,14 @@ int guarded(scs_ctx* c, F&& f) {
   }
 }
 
+// zero = false: the caller's next kernel writes every element (the device door's re-tile)
 template <class T>
-T* dalloc(scs_ctx* c, size_t n) {
+T* dalloc(scs_ctx* c, size_t n, bool zero = true) {
   void* p = nullptr;
   const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
   hipError_t e = hipMalloc(&p, bytes);
   if (e != hipSuccess) fail(c, SCS_ERR_HIP, "hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
-  HCK(hipMemsetAsync(p, 0, bytes, c->st));
+  if (zero) HCK(hipMemsetAsync(p, 0, bytes, c->st));
   c->allocs.push_back({p, bytes});
   return (T*)p;
 }
@@ -869,8 +870,8 @@ void invalidate_caches(scs_ctx* c) {
 size_t a_block_bytes(const scs_ctx* c, int64_t rows, int a32) {
   return (size_t)rows * c->mpad * (a32 ? sizeof(float) : sizeof(double));
 }
-double* alloc_A(scs_ctx* c, int64_t rows, int a32) {
-  return dalloc<double>(c, a_block_bytes(c, rows, a32) / sizeof(double));
+double* alloc_A(scs_ctx* c, int64_t rows, int a32, bool zero = true) {
+  return dalloc<double>(c, a_block_bytes(c, rows, a32) / sizeof(double), zero);
 }
 
 // exchange the context's N-dependent fields with v (the full data <-> a minibatch)
@@ -2727,30 +2728,133 @@ static void refuse_f32_quadratic(scs_ctx* c, int a32) {
                          "scs_set_data_f32) does not cover it");
 }
 
-// scs_set_data (in32 = 0) / scs_set_data_f32 (in32 = 1: host floats, stored as they are)
-static int set_data_any(scs_ctx* c, int64_t N, int64_t m, const void* A, int in32, int64_t lda, const double* y,
-                        int64_t Nglob, int64_t row0) {
-  if (is_group(c)) return group_set_data(c, N, m, A, in32, lda, y, Nglob, row0);
+// Where the rows of a dense block come from.  Host (dev = 0): column-major rows with leading
+// dimension lda, in32: float elements.  Device (dev = 1, scs_set_data_device): element (n, j) at
+// A[n*sn + j*sm], in32 likewise; src_stream: the producer's stream, or NULL.
+struct DenseSrc {
+  const void* A;
+  int in32;
+  int64_t lda;
+  int dev = 0;
+  int64_t sn = 0, sm = 0;
+  hipStream_t src_stream = nullptr;
+  int elem_bytes = 0;           // as the caller gave it (checked before in32 means anything)
+  const char* what = nullptr;   // the entry point, for messages
+};
+
+// hipPointerGetAttributes on plain host memory: "unregistered" on current runtimes, an error (left
+// in the thread's last-error slot, cleared here) on older ones
+static bool is_device_ptr(const void* p, int* dev_out) {
+  hipPointerAttribute_t at;
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  if (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged) return false;
+  if (dev_out) *dev_out = at.device;
+  return true;
+}
+
+static int refuse_group_device(scs_ctx* g, const char* what) {
+  set_err(g, "%s takes a single-device context (scs_create): a multi-device context would have to split the "
+             "device array across its devices", what);
+  return SCS_ERR_ARG;
+}
+
+// the refusals of a device source, all before anything is queued or freed; `what` names the entry
+static void check_device_src(scs_ctx* c, const DenseSrc& s, int64_t N, int64_t m) {
+  const char* what = s.what;
+  const int elem_bytes = s.elem_bytes;
+  if (elem_bytes != 4 && elem_bytes != 8)
+    fail(c, SCS_ERR_ARG, "%s: elem_bytes = %d (8: double, 4: float)", what, elem_bytes);
+  if (N < 0 || m <= 0) fail(c, SCS_ERR_ARG, "%s: bad dimensions N=%lld m=%lld", what, (long long)N, (long long)m);
+  if (s.sn != 1 && s.sm != 1)
+    fail(c, SCS_ERR_ARG, "%s: both strides are non-unit (%lld, %lld): one of stride_n, stride_m must be 1 "
+                         "(make the array contiguous)", what, (long long)s.sn, (long long)s.sm);
+  const bool rows = s.sm == 1 && (s.sn != 1 || N <= 1);   // launch_tile_device's choice of layout
+  if (rows ? (N > 1 && s.sn < m) : (m > 1 && s.sm < N))
+    fail(c, SCS_ERR_ARG, "%s: stride_%s = %lld is smaller than the extent it spans (%lld)", what, rows ? "n" : "m",
+         (long long)(rows ? s.sn : s.sm), (long long)(rows ? m : N));
+  if (!s.A) fail(c, SCS_ERR_ARG, "%s: dA is NULL", what);
+  if (N == 0) return;
+  int dev = -1;
+  if (!is_device_ptr(s.A, &dev))
+    fail(c, SCS_ERR_ARG, "%s: dA is not device memory (hipPointerGetAttributes); host rows go through "
+                         "scs_set_data", what);
+  if (dev != c->dev)
+    fail(c, SCS_ERR_ARG, "%s: dA lives on device %d, the context on device %d", what, dev, c->dev);
+  // the matrix must lie inside its allocation (where the runtime can tell)
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)s.A) == hipSuccess) {
+    const int64_t last = rows ? (N - 1) * s.sn + (m - 1) : (m - 1) * s.sm + (N - 1);
+    const char* end = (const char*)s.A + (size_t)(last + 1) * elem_bytes;
+    if (end > (const char*)base + size)
+      fail(c, SCS_ERR_ARG, "%s: the strided matrix runs past the end of dA's allocation", what);
+  } else {
+    (void)hipGetLastError();
+  }
+}
+
+// N rows of src -> the context's (current view's) A and y.  Host rows: panel by panel through the
+// column-major staging buffer.  Device rows: one re-tile pass that writes the whole block, padding
+// included.  Ends with the stream drained: the caller may free the source.
+static void load_dense(scs_ctx* c, const DenseSrc& s, int64_t N, const double* y) {
+  if (s.dev) {
+    // __cuda_array_interface__'s two small integers are no handles, and a runtime that does not know
+    // hipStreamLegacy reads (hipStream_t)1 as an object: neither value ever reaches the runtime as one.
+    // 1, the legacy default stream, is the NULL stream; 2, the caller's per-thread default stream, is
+    // covered by a device-wide synchronise.
+    const uintptr_t sv = (uintptr_t)s.src_stream;
+    if (sv == 2) {
+      HCK(hipDeviceSynchronize());
+    } else if (sv) {   // the work queued on the producer's stream so far
+      hipEvent_t ev;
+      HCK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+      hipError_t e = hipEventRecord(ev, sv == 1 ? (hipStream_t) nullptr : s.src_stream);
+      if (e == hipSuccess) e = hipStreamWaitEvent(c->st, ev, 0);
+      (void)hipEventDestroy(ev);
+      HCK(e);
+    }
+    const bool ydev = y && is_device_ptr(y, nullptr);
+    HCK(launch_tile_device(s.A, s.in32, s.sn, s.sm, N, c->m, c->Npad, c->mpad, c->A, c->a32, c->st));
+    if (y && N > 0)
+      HCK(hipMemcpyAsync(c->y, y, sizeof(double) * N, ydev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->st));
+    sync(c);
+    return;
+  }
+  if (N <= 0) return;
+  double* C = dalloc<double>(c, (size_t)c->Npad * (s.in32 ? 64 : 128));   // Npad x 128 elements
+  upload_panels(c, s.A, s.in32, N, s.lda, c->Npad, c->A, c->a32, C);
+  sync(c);
+  dfree_t(c, C);
+  if (y) h2d(c, c->y, y, N);
+}
+
+// scs_set_data (in32 = 0) / scs_set_data_f32 (in32 = 1: host floats, stored as they are) /
+// scs_set_data_device (src.dev: the mode alone decides the stored type)
+static int set_data_any(scs_ctx* c, int64_t N, int64_t m, const DenseSrc& src, const double* y, int64_t Nglob,
+                        int64_t row0) {
+  const void* A = src.A;
+  const int in32 = src.dev ? 0 : src.in32;   // a host fp32 source switches the mode on
+  if (is_group(c)) {
+    if (src.dev) return refuse_group_device(c, src.what);
+    return group_set_data(c, N, m, A, in32, src.lda, y, Nglob, row0);
+  }
   return guarded(c, [&] {
     HCK(hipSetDevice(c->dev));
+    if (src.dev) check_device_src(c, src, N, m);
     if (A) refuse_f32_quadratic(c, in32 | c->dense_f32);
     if (in32 && A) c->dense_f32 = 1;
     reset_data(c);
     set_dims(c, N, m, Nglob, row0);
     c->generic = (A == nullptr);
     if (!c->generic) {
-      if (lda < N) fail(c, SCS_ERR_ARG, "lda (%lld) < N (%lld)", (long long)lda, (long long)N);
+      if (!src.dev && src.lda < N) fail(c, SCS_ERR_ARG, "lda (%lld) < N (%lld)", (long long)src.lda, (long long)N);
       c->a32 = c->dense_f32;
-      c->A = alloc_A(c, c->Npad, c->a32);
+      c->A = alloc_A(c, c->Npad, c->a32, !src.dev);
       c->y = dalloc<double>(c, c->Npad);
-      if (N > 0) {
-        // panel by panel: host columns -> column-major staging buffer -> panel-blocked A
-        double* C = dalloc<double>(c, (size_t)c->Npad * (in32 ? 64 : 128));   // Npad x 128 elements
-        upload_panels(c, A, in32, N, lda, c->Npad, c->A, c->a32, C);
-        sync(c);
-        dfree_t(c, C);
-        if (y) h2d(c, c->y, y, N);
-      }
+      load_dense(c, src, N, y);
     }
     alloc_mspace(c);
     alloc_nspace(c);
@@ -2761,7 +2865,25 @@ static int set_data_any(scs_ctx* c, int64_t N, int64_t m, const void* A, int in3
 
 int scs_set_data(scs_ctx* c, int64_t N, int64_t m, const double* A, int64_t lda, const double* y, int64_t Nglob,
                  int64_t row0) {
-  return set_data_any(c, N, m, A, 0, lda, y, Nglob, row0);
+  return set_data_any(c, N, m, DenseSrc{A, 0, lda}, y, Nglob, row0);
+}
+
+static DenseSrc device_src(const char* what, const void* dA, int elem_bytes, int64_t sn, int64_t sm, void* stream) {
+  DenseSrc s{dA, elem_bytes == 4, 0};
+  s.dev = 1;
+  s.sn = sn;
+  s.sm = sm;
+  s.src_stream = (hipStream_t)stream;
+  s.elem_bytes = elem_bytes;
+  s.what = what;
+  return s;
+}
+
+int scs_set_data_device(scs_ctx* c, int64_t N, int64_t m, const void* dA, int elem_bytes, int64_t stride_n,
+                        int64_t stride_m, const double* y, void* src_stream, int64_t Nglob, int64_t row0) {
+  if (!c) return SCS_ERR_ARG;
+  return set_data_any(c, N, m, device_src("scs_set_data_device", dA, elem_bytes, stride_n, stride_m, src_stream), y,
+                      Nglob, row0);
 }
 
 int scs_set_data_f32(scs_ctx* c, int64_t N, int64_t m, const void* A32, int64_t lda, const double* y, int64_t Nglob,
@@ -2770,7 +2892,7 @@ int scs_set_data_f32(scs_ctx* c, int64_t N, int64_t m, const void* A32, int64_t 
     c->err = "scs_set_data_f32: A32 is NULL (a ProblemGeneric goes through scs_set_data)";
     return SCS_ERR_ARG;
   }
-  return set_data_any(c, N, m, A32, 1, lda, y, Nglob, row0);
+  return set_data_any(c, N, m, DenseSrc{A32, 1, lda}, y, Nglob, row0);
 }
 
 int scs_set_dense_f32(scs_ctx* c, int on) {
@@ -3065,7 +3187,7 @@ int scs_get_sparse(scs_ctx* c, int64_t* rowptr, int32_t* colidx, double* val) {
 
 // ---- held-out data (Problem(...; Atest, ytest), problems.jl:27-28,67-68) -----------------------
 // the rows of a new held-out view (after free_test): Npad, nstage and the buffers of its dense form
-static void test_view_dims(scs_ctx* c, int64_t N, int64_t Nglob, bool sparse) {
+static void test_view_dims(scs_ctx* c, int64_t N, int64_t Nglob, bool sparse, bool zero_A = true) {
   if (!c->has_data || c->generic)
     fail(c, SCS_ERR_STATE, "test data needs a data problem: call scs_set_data / scs_gen_data / scs_set_sparse first");
   if (N < 0) fail(c, SCS_ERR_ARG, "test data: N = %lld", (long long)N);
@@ -3078,16 +3200,27 @@ static void test_view_dims(scs_ctx* c, int64_t N, int64_t Nglob, bool sparse) {
   v.y = dalloc<double>(c, v.Npad);
   if (!sparse) {   // dense held-out rows follow the context's storage mode
     v.a32 = c->dense_f32;
-    v.A = alloc_A(c, v.Npad, v.a32);
+    v.A = alloc_A(c, v.Npad, v.a32, zero_A);
   }
 }
 
 // scs_set_test_data (in32 = 0) / scs_set_test_data_f32 (in32 = 1)
-static int set_test_any(scs_ctx* c, int64_t N, const void* A, int in32, int64_t lda, const double* y, int64_t Nglob,
-                        int64_t row0) {
-  if (is_group(c)) return group_set_test_data(c, N, A, in32, lda, y, Nglob, row0);
+static int set_test_any(scs_ctx* c, int64_t N, const DenseSrc& src, const double* y, int64_t Nglob, int64_t row0) {
+  const void* A = src.A;
+  const int in32 = src.dev ? 0 : src.in32;
+  const int64_t lda = src.dev ? N : src.lda;
+  if (is_group(c)) {
+    if (src.dev) return refuse_group_device(c, src.what);
+    return group_set_test_data(c, N, A, in32, lda, y, Nglob, row0);
+  }
   return guarded(c, [&] {
     HCK(hipSetDevice(c->dev));
+    if (src.dev) {
+      if (!y) fail(c, SCS_ERR_ARG, "%s: y is NULL (dA and y are both required)", src.what);
+      if (!c->has_data || c->generic)
+        fail(c, SCS_ERR_STATE, "test data needs a data problem: call scs_set_data / scs_gen_data / scs_set_sparse first");
+      check_device_src(c, src, N, c->m);
+    }
     if (A && y) refuse_f32_quadratic(c, in32 | c->dense_f32);
     if (in32 && A) c->dense_f32 = 1;
     free_test(c);
@@ -3098,15 +3231,9 @@ static int set_test_any(scs_ctx* c, int64_t N, const void* A, int in32, int64_t 
     }
     if (lda < N) fail(c, SCS_ERR_ARG, "test data: lda (%lld) < N (%lld)", (long long)lda, (long long)N);
     (void)row0;
-    test_view_dims(c, N, Nglob, false);
+    test_view_dims(c, N, Nglob, false, !src.dev);
     TestScope ts(c);
-    if (N > 0) {
-      double* C = dalloc<double>(c, (size_t)c->Npad * 128);
-      upload_panels(c, A, in32, N, lda, c->Npad, c->A, c->a32, C);
-      h2d(c, c->y, y, N);
-      sync(c);
-      dfree_t(c, C);
-    }
+    load_dense(c, src, N, y);
     alloc_nspace(c);
     sync(c);
     c->tset.on = true;
@@ -3115,12 +3242,19 @@ static int set_test_any(scs_ctx* c, int64_t N, const void* A, int in32, int64_t 
 
 int scs_set_test_data(scs_ctx* c, int64_t N, const double* A, int64_t lda, const double* y, int64_t Nglob,
                       int64_t row0) {
-  return set_test_any(c, N, A, 0, lda, y, Nglob, row0);
+  return set_test_any(c, N, DenseSrc{A, 0, lda}, y, Nglob, row0);
+}
+
+int scs_set_test_data_device(scs_ctx* c, int64_t N, const void* dA, int elem_bytes, int64_t stride_n,
+                             int64_t stride_m, const double* y, void* src_stream, int64_t Nglob, int64_t row0) {
+  if (!c) return SCS_ERR_ARG;
+  return set_test_any(c, N, device_src("scs_set_test_data_device", dA, elem_bytes, stride_n, stride_m, src_stream), y,
+                      Nglob, row0);
 }
 
 int scs_set_test_data_f32(scs_ctx* c, int64_t N, const void* A32, int64_t lda, const double* y, int64_t Nglob,
                           int64_t row0) {
-  return set_test_any(c, N, A32, 1, lda, y, Nglob, row0);
+  return set_test_any(c, N, DenseSrc{A32, 1, lda}, y, Nglob, row0);
 }
 
 int scs_set_test_sparse(scs_ctx* c, int64_t N, int64_t nnz, const int64_t* rowptr, const int32_t* colidx,
@@ -4696,7 +4830,7 @@ int group_set_data(scs_ctx* g, int64_t N, int64_t m, const void* A, int in32, in
   g->plan = A ? row_plan(N, n) : std::vector<RowBlock>((size_t)n);
   const int rc = group_run(g, [&](scs_ctx* s, int i) {
     const RowBlock b = g->plan[(size_t)i];
-    return set_data_any(s, A ? b.rows() : 0, m, A ? (const char*)A + es * b.r0 : nullptr, in32, lda,
+    return set_data_any(s, A ? b.rows() : 0, m, DenseSrc{A ? (const char*)A + es * b.r0 : nullptr, in32, lda},
                         y ? y + b.r0 : nullptr, A ? N : 0, b.r0);
   });
   if (rc == SCS_OK) {
@@ -4753,8 +4887,8 @@ int group_set_test_data(scs_ctx* g, int64_t N, const void* A, int in32, int64_t 
   const std::vector<RowBlock> plan = row_plan(std::max<int64_t>(N, 0), (int)g->subs.size());
   return group_run(g, [&](scs_ctx* s, int i) {
     const RowBlock b = plan[(size_t)i];
-    return set_test_any(s, b.rows(), A ? (const char*)A + es * b.r0 : nullptr, in32, lda, y ? y + b.r0 : nullptr, N,
-                        b.r0);
+    return set_test_any(s, b.rows(), DenseSrc{A ? (const char*)A + es * b.r0 : nullptr, in32, lda},
+                        y ? y + b.r0 : nullptr, N, b.r0);
   });
 }
 

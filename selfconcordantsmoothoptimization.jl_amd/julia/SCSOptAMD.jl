@@ -15,7 +15,7 @@ using SelfConcordantSmoothOptimization
 import SelfConcordantSmoothOptimization: step!, init!, ProximalMethod, ProxModel, is_interval_set
 
 export DeviceProblem, configure!, iterate_device!, set_gram_cache!, set_solver!, rccl_unique_id, set_comm_rccl!,
-       set_comm_callback!, set_test!, set_compute_f32!, fallback_counts, data_info
+       set_comm_callback!, set_test!, set_test_device!, set_compute_f32!, fallback_counts, data_info
 
 const lib = joinpath(@__DIR__, "..", "scsopt", "libscsopt.so")
 
@@ -178,6 +178,54 @@ function DeviceProblem(A::Matrix{Float32}, y::AbstractVector, x0::Vector{Float64
               ctx, N, m, A, N, yv, N_global, row0), ctx)
     model = finish_problem(ctx, A, yv, x0, loss, λ, out_fn, scale, L, sol, C_set, P)
     return set_test!(model, Atest, ytest; Ntest_global, test_row0)
+end
+
+# A that is already on the GPU (scs_set_data_device): `ptr` is device memory on `device`, element (n, j)
+# of the N x m matrix at ptr[n*strides[1] + j*strides[2]] (strides in elements, one of them 1), elements
+# of type `elem` (Float64 or Float32).  A column-major ROCArray{T,2} is strides = (1, size(A, 1)), its
+# default here; a row-major buffer is strides = (m, 1).  The matrix is re-tiled on the device: no host
+# copy.  dense_f32 alone decides the stored type (a Float32 source with dense_f32 = false is widened, a
+# Float64 one with dense_f32 = true rounded on the device).  y: a host vector, or a Ptr{Cvoid} to N
+# device Float64.  stream: the HIP stream that produced A (C_NULL: the caller has synchronised).  The
+# call returns with the copy done, so A may be freed.  Single-device contexts only.
+# Written against the header; never executed (no Julia / AMDGPU.jl on the build machines).
+device_y(y::Ptr{Cvoid}, N) = (y, convert(Ptr{Float64}, y))
+function device_y(y::AbstractVector, N)
+    yv = Vector{Float64}(y)
+    length(yv) == N || throw(DimensionMismatch("y has $(length(yv)) entries, A has $N rows"))
+    return (yv, pointer(yv))
+end
+
+function DeviceProblem(ptr::Ptr{Cvoid}, N::Integer, m::Integer, y::Union{AbstractVector,Ptr{Cvoid}},
+                       x0::Vector{Float64}, loss::Symbol, λ;
+                       elem::Type=Float64, strides::Tuple{Integer,Integer}=(1, N), dense_f32::Bool=false,
+                       stream::Ptr{Cvoid}=C_NULL,
+                       out_fn::Union{Symbol,Nothing}=nothing, scale::Float64=1.0 / N,
+                       L=nothing, sol::Vector{Float64}=zero(x0), C_set=nothing, P=nothing, device::Integer=0,
+                       N_global::Integer=N, row0::Integer=0)
+    (elem === Float64 || elem === Float32) || throw(ArgumentError("elem is Float64 or Float32"))
+    length(x0) == m || throw(DimensionMismatch("x0 has $(length(x0)) entries, A has $m columns"))
+    ctx = create_ctx(device, nothing, :rccl)
+    chk(ccall((:scs_set_dense_f32, lib), Cint, (Ptr{Cvoid}, Cint), ctx, dense_f32 ? 1 : 0), ctx)
+    yroot, yp = device_y(y, N)
+    GC.@preserve yroot chk(ccall((:scs_set_data_device, lib), Cint,
+              (Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Cint, Int64, Int64, Ptr{Float64}, Ptr{Cvoid}, Int64, Int64),
+              ctx, N, m, ptr, sizeof(elem), strides[1], strides[2], yp, stream, N_global, row0), ctx)
+    return finish_problem(ctx, nothing, y isa Ptr ? nothing : yroot, x0, loss, λ, out_fn, scale, L, sol, C_set, P)
+end
+
+# held-out rows from device memory (scs_set_test_data_device), as DeviceProblem(ptr, ...) takes A
+function set_test_device!(model::DeviceProblem, ptr::Ptr{Cvoid}, Ntest::Integer,
+                          ytest::Union{AbstractVector,Ptr{Cvoid}}; elem::Type=Float64,
+                          strides::Tuple{Integer,Integer}=(1, Ntest), stream::Ptr{Cvoid}=C_NULL,
+                          Ntest_global::Integer=0, test_row0::Integer=0)
+    (elem === Float64 || elem === Float32) || throw(ArgumentError("elem is Float64 or Float32"))
+    yroot, yp = device_y(ytest, Ntest)
+    GC.@preserve yroot chk(ccall((:scs_set_test_data_device, lib), Cint,
+              (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Cint, Int64, Int64, Ptr{Float64}, Ptr{Cvoid}, Int64, Int64),
+              model.ctx, Ntest, ptr, sizeof(elem), strides[1], strides[2], yp, stream, Ntest_global, test_row0),
+        model.ctx)
+    return model
 end
 
 # (element bytes of the dense A: 8 or 4, bytes of that block, device bytes the context holds)

@@ -113,10 +113,14 @@ _SIGS = {
     "scs_set_data_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, c_dp, C.c_int64,
                                    C.c_int64]),
     "scs_data_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), c_i64p, c_i64p]),
+    "scs_set_data_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_int64,
+                                      C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]),
     "scs_get_data": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, c_dp, C.c_int64, c_dp]),
     "scs_get_dims": (C.c_int, [C.c_void_p, c_i64p, c_i64p, c_i64p, c_i64p]),
     "scs_set_test_data": (C.c_int, [C.c_void_p, C.c_int64, c_dp, C.c_int64, c_dp, C.c_int64, C.c_int64]),
     "scs_set_test_data_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, c_dp, C.c_int64, C.c_int64]),
+    "scs_set_test_data_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_int64,
+                                           C.c_void_p, C.c_void_p, C.c_int64, C.c_int64]),
     "scs_set_test_sparse": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, c_i64p, c_i32p, c_dp, C.c_int, c_dp,
                                       C.c_int64, C.c_int64]),
     "scs_gen_test_data": (C.c_int, [C.c_void_p, C.POINTER(Synth)]),
@@ -197,6 +201,74 @@ def dptr(a):
         return None
     assert a.dtype == np.float64 and a.flags["C_CONTIGUOUS"], "expected a contiguous float64 array"
     return a.ctypes.data_as(c_dp)
+
+
+def is_device_array(a):
+    """An object that exposes __cuda_array_interface__ (a torch-ROCm tensor, a CuPy array, ...)."""
+    if a is None or isinstance(a, np.ndarray):
+        return False
+    try:   # a torch CPU tensor has the attribute and raises from it: a host array, as before
+        return isinstance(a.__cuda_array_interface__, dict)
+    except Exception:
+        return False
+
+
+def parse_device_matrix(iface):
+    """A 2-D __cuda_array_interface__ dict -> what scs_set_data_device takes:
+    {"ptr", "N", "m", "elem_bytes", "stride_n", "stride_m", "stream"}; strides in elements, one of them
+    1.  "<f8" and "<f4" are accepted (anything else: TypeError); two non-unit strides raise ValueError
+    -- the binding never copies silently.  strides = None means C-contiguous.  `stream` is the
+    interface's value: None (the producer is done), 1 (the legacy default stream), 2 (the per-thread
+    default stream) -- scs_set_data_device takes both as src_stream and resolves them itself -- or a
+    stream handle."""
+    typestr = iface["typestr"]
+    if typestr not in ("<f8", "<f4"):
+        raise TypeError(f"device array of type {typestr!r}: float64 ('<f8') or float32 ('<f4') is needed")
+    es = 8 if typestr == "<f8" else 4
+    shape = tuple(int(v) for v in iface["shape"])
+    if len(shape) != 2:
+        raise ValueError(f"a device matrix has two dimensions, this array has shape {shape}")
+    N, m = shape
+    strides = iface.get("strides")
+    if strides is None:
+        sn, sm = m, 1
+    else:
+        if any(int(b) % es for b in strides):
+            raise ValueError(f"device array strides {tuple(strides)} are not multiples of the element size {es}")
+        sn, sm = (int(b) // es for b in strides)
+    # the stride of an extent-1 axis addresses nothing: take the contiguous value
+    if N == 1 and sm != 1:
+        sn = 1
+    elif N == 1:
+        sn = max(sn, m)
+    if m == 1 and sn != 1:
+        sm = 1
+    elif m == 1:
+        sm = max(sm, N)
+    if sn != 1 and sm != 1:
+        raise ValueError(f"device array with strides ({sn}, {sm}) elements: one axis must be contiguous -- pass "
+                         "a contiguous array (x.contiguous() / cupy.ascontiguousarray); it is not copied here")
+    if sn < 0 or sm < 0 or (sm == 1 and N > 1 and sn < m) or (sn == 1 and sm != 1 and m > 1 and sm < N):
+        raise ValueError(f"device array with strides ({sn}, {sm}) elements overlaps itself for shape {shape}")
+    ptr, _readonly = iface["data"]
+    stream = iface.get("stream")
+    if stream is not None and int(stream) == 0:
+        raise ValueError("__cuda_array_interface__ forbids stream = 0 (1 and 2 name the default streams)")
+    return {"ptr": int(ptr) if ptr else 0, "N": N, "m": m, "elem_bytes": es, "stride_n": sn, "stride_m": sm,
+            "stream": None if stream is None else int(stream)}
+
+
+def parse_device_vector(iface, n):
+    """A device y: n contiguous float64 -> its pointer."""
+    if iface["typestr"] != "<f8":
+        raise TypeError(f"a device y must be float64, got {iface['typestr']!r}")
+    shape = tuple(int(v) for v in iface["shape"])
+    if shape != (n,):
+        raise ValueError(f"y has shape {shape}, expected ({n},)")
+    strides = iface.get("strides")
+    if strides is not None and n > 1 and int(strides[0]) != 8:
+        raise ValueError("a device y must be contiguous")
+    return int(iface["data"][0] or 0)
 
 
 class Context:

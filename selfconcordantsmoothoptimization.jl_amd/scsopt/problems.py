@@ -10,6 +10,7 @@ host.  Row sharding: pass ``comm=shard.Comm(...)`` and the local rows.
 from __future__ import annotations
 
 import ctypes as C
+import sys
 import logging
 from dataclasses import dataclass
 from typing import Any, Optional
@@ -116,6 +117,9 @@ class Problem:
             A, y, self.generic = None, None, True
         if devices is not None and (comm is not None or _is_sparse(A)):
             raise ValueError("devices=[...] (one process, several GPUs) takes a dense A and no comm")
+        if devices is not None and (_lib.is_device_array(A) or _lib.is_device_array(Atest)):
+            raise ValueError("devices=[...] splits host rows across its GPUs: a device array lives on one of them "
+                             "(pass a host array, or one process per GPU with a row slice each)")
         self.ctx = _ctx if _ctx is not None else _lib.Context(device, devices=devices, device_exchange=device_exchange)
         # dense_f32: a dense A (and dense held-out rows) stored as fp32 on the device, fp64 arithmetic --
         # bit for bit what the same values widened to fp64 give (scs_set_dense_f32)
@@ -128,6 +132,8 @@ class Problem:
                 self.ctx.check(_lib.lib.scs_set_data(self.ctx.h, 0, self.m, None, 0, None, 0, 0))
             elif _is_sparse(A):
                 self._set_sparse(A, y, N_global, row0, f32=bool(sparse_f32))
+            elif _lib.is_device_array(A):
+                self.N = self._set_device(A, y, False, N_global, row0)
             else:
                 # a float32 matrix goes to the device as it is only with dense_f32; the default widens it
                 as32 = self.dense_f32 and isinstance(A, np.ndarray) and A.dtype == np.float32
@@ -205,6 +211,12 @@ class Problem:
             self.ctx.check(_lib.lib.scs_set_test_callback(self.ctx.h, 1))
             self.test_model = True
             return
+        if _lib.is_device_array(Atest):
+            if len(self.ctx.devices) > 1:
+                raise ValueError("a devices=[...] problem takes host held-out rows, not a device array")
+            self._set_device(Atest, ytest, True, Ntest_global, row0)
+            self.test_model = True
+            return
         yv = np.ascontiguousarray(np.asarray(ytest, dtype=np.float64).reshape(-1))
         Ng = int(Ntest_global) if Ntest_global is not None else 0
         if _is_sparse(Atest):
@@ -232,6 +244,52 @@ class Problem:
                 self.ctx.check(_lib.lib.scs_set_test_data(self.ctx.h, int(At.shape[0]), Af.ctypes.data_as(_lib.c_dp),
                                                           int(At.shape[0]), dptr(yv), Ng, int(row0)))
         self.test_model = True
+
+    def _set_device(self, A, y, test, N_global, row0):
+        """A (and possibly y) already on the GPU, through __cuda_array_interface__ (a torch-ROCm tensor, a
+        CuPy array): scs_set_data_device / scs_set_test_data_device re-tile it on the device, no host
+        copy.  Row- or column-major, float64 or float32; the stored type follows dense_f32 as for host
+        arrays (float32 kept only with dense_f32=True, float64 rounded on the device with it).
+        Returns N."""
+        torch_stream = None
+        for a in (A, y):
+            if type(a).__module__.split(".")[0] == "torch":
+                _lib.require_torch_runtime("a torch tensor as A / y")   # a second runtime's pointer is not ours
+                torch_stream = sys.modules["torch"].cuda.current_stream(a.device)
+        d = _lib.parse_device_matrix(A.__cuda_array_interface__)
+        if d["m"] != self.m:
+            raise ValueError(f"A must be N x m with m = length(x0) = {self.m}")
+        N = d["N"]
+        if _lib.is_device_array(y):
+            yi = y.__cuda_array_interface__
+            yp, yv = _lib.parse_device_vector(yi, N), None
+            ystream = yi.get("stream")
+        else:
+            yv = np.ascontiguousarray(np.asarray(y, dtype=np.float64).reshape(-1))
+            if yv.shape[0] != N:
+                raise ValueError(f"y has {yv.shape[0]} entries, A has {N} rows")
+            yp, ystream = yv.ctypes.data, None
+        stream = d["stream"]
+        if stream is None and ystream is not None:
+            stream = int(ystream)
+        if stream is None and torch_stream is not None:
+            # torch's interface names no stream: the tensor's producer is the current one (its default
+            # stream is drained here: a handle of 0 would read as "the source is complete")
+            if torch_stream.cuda_stream:
+                stream = int(torch_stream.cuda_stream)
+            else:
+                torch_stream.synchronize()
+        if self.dense_f32:
+            self.ctx.check(_lib.lib.scs_set_dense_f32(self.ctx.h, 1))
+        Ng = 0 if N_global is None else int(N_global)
+        if test:
+            rc = _lib.lib.scs_set_test_data_device(self.ctx.h, N, d["ptr"], d["elem_bytes"], d["stride_n"],
+                                                   d["stride_m"], yp, stream, Ng, int(row0))
+        else:
+            rc = _lib.lib.scs_set_data_device(self.ctx.h, N, self.m, d["ptr"], d["elem_bytes"], d["stride_n"],
+                                              d["stride_m"], yp, stream, Ng if Ng else N, int(row0))
+        self.ctx.check(rc)
+        return N
 
     def gen_test(self, Ntest, *, row0=None, seed=1234, kind=1, density=0.1):
         """Held-out rows of the synthetic generator: rows [row0, row0 + Ntest) with row0 = N_global
