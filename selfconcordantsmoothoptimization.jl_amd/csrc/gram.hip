@@ -31,6 +31,7 @@
 // distinct column panels, which its 4 MiB L2 serves (speed only; results do
 // not depend on placement).
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 #include <vector>
@@ -41,6 +42,7 @@ namespace scs {
 
 }  // namespace scs
 #include "gram_strip.h"   // GT, GBK, swz, the GRAM_* flags and the latency strip body
+#include "gram_tiles.h"   // the 256 x 128 tile list and its pair items
 namespace scs {
 
 // Workgroup barrier that orders LDS only: the staged global loads (two stages
@@ -591,15 +593,13 @@ void gram_tile_list(int nb, int2* out, int* ntiles) {
 // Super-blocked list of 256 x 128 tiles (BI, bj) for the TI = 4 kernel: row block
 // BI covers 128-blocks 2BI, 2BI+1; every tile with bj <= 2BI+1 (the one above the
 // diagonal holds the mirror values, stored harmlessly below it).  nb even.
+// _paired: the tiles (I, 2I+1) of two row blocks as one pair item (gram_tiles.h) -- the list of the
+// unpacked launches of the interleaved 256 x 128 kernels, which alone decode it.
 void gram_tile_list_tall(int nb, int2* out, int* ntiles) {
-  const int nbi = nb / 2, SI = 4, SJ = 8;
-  int t = 0;
-  for (int sbi = 0; sbi < (nbi + SI - 1) / SI; ++sbi)
-    for (int sbj = 0; sbj <= sbi; ++sbj)
-      for (int I = sbi * SI; I < (sbi + 1) * SI && I < nbi; ++I)
-        for (int j = sbj * SJ; j < (sbj + 1) * SJ && j < nb; ++j)
-          if (j <= 2 * I + 1) out[t++] = make_int2(I, j);
-  *ntiles = t;
+  *ntiles = gram_tile_list_tall_t(nb, false, out, [](int x, int y) { return make_int2(x, y); });
+}
+void gram_tile_list_tall_paired(int nb, int2* out, int* ntiles) {
+  *ntiles = gram_tile_list_tall_t(nb, true, out, [](int x, int y) { return make_int2(x, y); });
 }
 
 // Row-major lower-triangle order: the first nb'(nb'+1)/2 entries are the list for nb' <= nb.
@@ -679,13 +679,28 @@ static int env_int(const char* name, int dflt) {
   const char* e = getenv(name);
   return e ? atoi(e) : dflt;
 }
+//   SCS_GRAM_SIA = 8 + bits (8 .. 15): the interleaved kernels, and on the fp64 256 x 128 ones the
+//                 issue order at the stage barriers (gram_sia_body.h E1 / E2 / E3; 8 = the order of
+//                 PIPE 1).  Unset: bit 2 (phase 2a opens with an MFMA group; C3 step -26 to -30 ms).
+//                 Built: 8, 10, 12 (other values run 8); DESIGN §7 has the arms measured.
 int gram_sia_mode() {
   static const int v = env_int("SCS_GRAM_SIA", 1);
-  return v;
+  return v >= 8 ? 1 : v;
+}
+constexpr int GRAM_EDGE_DEFAULT = 2;
+int gram_edge_bits() {
+  static const int v = env_int("SCS_GRAM_SIA", 1);
+  return v >= 8 && v <= 15 ? (v & 7) : GRAM_EDGE_DEFAULT;
 }
 int gram_tall_mode() {
   static const int v = env_int("SCS_GRAM_GLDS", 3);
   return v;
+}
+//   SCS_GRAM_DIAGPAIR (256 x 128 tiles): unset/1 = the unpacked launches' list pairs the diagonal's
+//                 D1 blocks (gram_tiles.h; the interleaved kernels only), 0 = the [U; D1] tiles.
+int gram_pair_ok() {
+  static const int v = env_int("SCS_GRAM_DIAGPAIR", 1);
+  return v != 0 && gram_tall_mode() == 3;
 }
 
 // The fused Aᵀv (AV kernels) rides on the default interleaved kernels.  Default: the 256 x 128
@@ -716,6 +731,20 @@ hipError_t gram_vfinal_launch(const double* VP, int npiece, int64_t vps, int64_t
 // the kernel of the latest main Gram launch (gram_launch / gram_launch_sched), as rocprofv3 names it
 static thread_local const char* g_main_name = "";   // per host thread: a multi-device context drives its devices from one thread each
 const char* gram_main_kernel_name() { return g_main_name; }
+
+// the fp64 256 x 128 interleaved kernel with the selected barrier-edge order (gram_edge_bits)
+template <bool AV, class... Args>
+static void sia_tall_launch(unsigned grid, hipStream_t st, Args... args) {
+  static thread_local char name[64];
+  int pipe = 1;
+  switch (gram_edge_bits()) {
+    case 2: pipe = 10; hipLaunchKernelGGL((gram_sia_kernel<10, 4, false, AV>), dim3(grid), dim3(512), 0, st, args...); break;
+    case 4: pipe = 12; hipLaunchKernelGGL((gram_sia_kernel<12, 4, false, AV>), dim3(grid), dim3(512), 0, st, args...); break;
+    default: hipLaunchKernelGGL((gram_sia_kernel<1, 4, false, AV>), dim3(grid), dim3(512), 0, st, args...);
+  }
+  snprintf(name, sizeof(name), "gram_sia_kernel<%d, 4, false, %s, false>", pipe, AV ? "true" : "false");
+  g_main_name = name;
+}
 
 hipError_t gram_launch(const void* Av, int a32, int64_t lda, const double* w, int64_t Nk, const int2* tiles,
                        int ntiles, double* G, int64_t ldg, int packed, int tall, hipStream_t st, const double* v,
@@ -750,9 +779,9 @@ hipError_t gram_launch(const void* Av, int a32, int64_t lda, const double* w, in
   const double* A = (const double*)Av;
   if (v) {
     if (tall) {
-      g_main_name = "gram_sia_kernel<1, 4, false, true, false>";
-      hipLaunchKernelGGL((gram_sia_kernel<1, 4, false, true>), dim3(ntiles), dim3(512), 0, st, A, lda, w, (int64_t)0,
-                         Nk, tiles, ntiles, G, ldg, flags, nullptr, 0, 0, nullptr, v, VP, vps, nullptr, 0, nullptr, (int64_t)0);
+      sia_tall_launch<true>((unsigned)ntiles, st, A, lda, w, (int64_t)0, Nk, tiles, ntiles, G, ldg, flags,
+                            (const int4*)nullptr, 0, 0, (double*)nullptr, v, VP, vps, (unsigned*)nullptr, 0,
+                            (const double*)nullptr, (int64_t)0);
     } else {
       g_main_name = "gram_sia_kernel<1, 2, false, true, false>";
       hipLaunchKernelGGL((gram_sia_kernel<1, 2, false, true>), dim3(ntiles), dim3(256), 0, st, A, lda, w, (int64_t)0,
@@ -769,9 +798,9 @@ hipError_t gram_launch(const void* Av, int a32, int64_t lda, const double* w, in
     hipLaunchKernelGGL((gram_sia_kernel<1, 2>), dim3(ntiles), dim3(256), 0, st, A, lda, w, (int64_t)0, Nk, tiles,
                        ntiles, G, ldg, flags, nullptr, 0, 0, nullptr, nullptr, nullptr, (int64_t)0, nullptr, 0, nullptr, (int64_t)0);
   } else if (gram_tall_mode() == 3) {
-    g_main_name = "gram_sia_kernel<1, 4, false, false, false>";
-    hipLaunchKernelGGL((gram_sia_kernel<1, 4>), dim3(ntiles), dim3(512), 0, st, A, lda, w, (int64_t)0, Nk, tiles,
-                       ntiles, G, ldg, flags, nullptr, 0, 0, nullptr, nullptr, nullptr, (int64_t)0, nullptr, 0, nullptr, (int64_t)0);
+    sia_tall_launch<false>((unsigned)ntiles, st, A, lda, w, (int64_t)0, Nk, tiles, ntiles, G, ldg, flags,
+                           (const int4*)nullptr, 0, 0, (double*)nullptr, (const double*)nullptr, (double*)nullptr,
+                           (int64_t)0, (unsigned*)nullptr, 0, (const double*)nullptr, (int64_t)0);
   } else {
     g_main_name = "gram_glds_kernel<true, 1>";
     hipLaunchKernelGGL((gram_glds_kernel<true, 1>), dim3(ntiles), dim3(512), 0, st, A, lda, A, lda, w, (int64_t)0, Nk,
@@ -969,6 +998,11 @@ __global__ void gram_combine_kernel(const double* __restrict__ P, const int4* __
     for (int sp = 0; sp < nsplit; ++sp) sum += P[(int64_t)(it.w + sp) * GTI * GT + e];
     double* dst = (packed & 1) ? G + ((int64_t)it.z * (GTI / GT) + il / GT) * GT * GT + jl * GT + (il % GT)
                                : G + ((int64_t)it.x * GTI + il) * ldg + (int64_t)it.y * GT + jl;
+    if (TI == 4 && gram_item_is_pair(it.y)) {   // rows 0..127 / 128..255: the two D1 blocks (unpacked only)
+      int bi, bj;
+      gram_item_block(it.x, it.y, il / GT, &bi, &bj);
+      dst = G + ((int64_t)bi * GT + il % GT) * ldg + (int64_t)bj * GT + jl;
+    }
     if (packed & 2) *dst += sum;
     else *dst = sum;
   }
@@ -1008,17 +1042,16 @@ hipError_t gram_launch_sched(const void* Av, int a32, int64_t lda, const double*
                          (int64_t)0, scnt, sob);
     }
   } else if (v && tall) {
-    g_main_name = "gram_sia_kernel<1, 4, false, true, false>";
-    hipLaunchKernelGGL((gram_sia_kernel<1, 4, false, true>), dim3(8 * seglen), dim3(512), 0, st, A, lda, w,
-                       (int64_t)0, Nk, nullptr, 0, G, ldg, flags, work, seglen, nsplit, P, v, VP, vps, scnt, sob, nullptr, (int64_t)0);
+    sia_tall_launch<true>((unsigned)(8 * seglen), st, A, lda, w, (int64_t)0, Nk, (const int2*)nullptr, 0, G, ldg, flags,
+                          work, seglen, nsplit, P, v, VP, vps, scnt, sob, (const double*)nullptr, (int64_t)0);
   } else if (v) {
     g_main_name = "gram_sia_kernel<1, 2, false, true, false>";
     hipLaunchKernelGGL((gram_sia_kernel<1, 2, false, true>), dim3(8 * seglen), dim3(256), 0, st, A, lda, w,
                        (int64_t)0, Nk, nullptr, 0, G, ldg, flags, work, seglen, nsplit, P, v, VP, vps, scnt, sob, nullptr, (int64_t)0);
   } else if (tall && glds == 3) {
-    g_main_name = "gram_sia_kernel<1, 4, false, false, false>";
-    hipLaunchKernelGGL((gram_sia_kernel<1, 4>), dim3(8 * seglen), dim3(512), 0, st, A, lda, w, (int64_t)0, Nk,
-                       nullptr, 0, G, ldg, flags, work, seglen, nsplit, P, nullptr, nullptr, (int64_t)0, scnt, sob, nullptr, (int64_t)0);
+    sia_tall_launch<false>((unsigned)(8 * seglen), st, A, lda, w, (int64_t)0, Nk, (const int2*)nullptr, 0, G, ldg,
+                           flags, work, seglen, nsplit, P, (const double*)nullptr, (double*)nullptr, (int64_t)0, scnt,
+                           sob, (const double*)nullptr, (int64_t)0);
   } else if (tall && glds == 2) {
     g_main_name = "gram_glds_kernel<true, 1>";
     hipLaunchKernelGGL((gram_glds_kernel<true, 1>), dim3(8 * seglen), dim3(512), 0, st, A, lda, A, lda, w, (int64_t)0,
@@ -1121,10 +1154,11 @@ int gram_schedule(const int2* tiles, int ntiles, int slots_per_xcd, std::vector<
     }
     // diag_first_gti (r05): the whole tiles whose row block holds their column panel -- the tiles an
     // AV launch gives the fused Aᵀv, the longer ones -- first in the XCD's order, so they run in its
-    // first round instead of lengthening the last (order only: every tile's bits are the same)
+    // first round instead of lengthening the last (order only: every tile's bits are the same).
+    // A pair item (gram_tiles.h) owns the Aᵀv rows of both its panels: designated too.
     if (diag_first_gti > 0)
       std::stable_partition(seg[x].begin(), seg[x].end(), [&](const int4& it) {
-        return it.x == (int)((int64_t)it.y * GT / diag_first_gti);
+        return gram_item_designated(it.x, it.y, diag_first_gti);
       });
     for (int i = n - tail; i < n; ++i) {
       const int2 tl = tiles[t0 + i];

@@ -14,8 +14,20 @@
   constexpr int NMM = 2 * NTI * 4;    // MFMAs per fragment set (2 u x NTI x 4)
   constexpr int NRD = NTI + 4;        // ds_read_b128 per fragment set
   constexpr int TAIL = NMM / 4;       // MFMAs left for phase 2b (1/8 and 3/8 measured within noise)
+  // PIPE >= 8: the interleaved schedule with the issue order at the stage barriers changed (the MFMA
+  // order per accumulator is untouched), one bit per edge:
+  //   1 (E1) phase 1: each fragment read ahead of its MFMA group (the last read has a group behind
+  //          it before lgkmcnt(0), not the barrier);
+  //   2 (E2) phase 2a head: one MFMA group ahead of the vmcnt wait, the w products and the addresses;
+  //   4 (E3) phase 2a tail: each ds_write ahead of its MFMA group.
+  constexpr bool E1 = PIPE >= 8 && (PIPE & 1), E2 = PIPE >= 8 && (PIPE & 2), E3 = PIPE >= 8 && (PIPE & 4);
+  // pair items (gram_tiles.h: the D1 blocks of two row blocks in one 256 x 128 tile) are decoded by
+  // the panel-blocked 256 x 128 kernels; their A2 stage block is the A1 block times w (256 rows)
+  constexpr bool PAIRT = TI == 4 && !CM && !BND;
+  constexpr int LBR = PAIRT ? GTI : GT;   // rows of the A2 stage block
+  constexpr int NAV = PAIRT ? NA : NB;    // Aᵀv chunks per thread per stage
   const int packed = flags & GRAM_PACKED, accumulate = flags & GRAM_ACCUMULATE, upper = flags & GRAM_UPPER;
-  __shared__ __attribute__((aligned(16))) double lds[(GTI + GT) * GBK];
+  __shared__ __attribute__((aligned(16))) double lds[(GTI + LBR) * GBK];
   const int orig = blockIdx.x;
   const int xcd = orig % 8;
   int bi, bj, tix, part = -1, piece = 0;
@@ -47,6 +59,17 @@
     bj = tl.y;
   }
 bnd_tile:
+  // the A1 panels of the tile: 2 bi, 2 bi + 1 (bi at 128 rows), or the two diagonal panels of a pair
+  // item, which then runs as tile "column panel pa" of rows [pa; pb]
+  int pa = (GTI / GT) * bi, pb = pa + 1;
+  bool pair = false;
+  if constexpr (PAIRT) {
+    if (gram_item_is_pair(bj)) {
+      pair = true;
+      gram_item_panels(bi, bj, &pa, &pb);
+      bj = pa;
+    }
+  }
   int tid_ = threadIdx.x;
   if constexpr (BND) asm volatile("" : "+v"(tid_));   // per tile: nothing derived from it is hoisted out of the loop
   const int tid = tid_, lane = tid & 63, wid = tid >> 6;
@@ -54,9 +77,10 @@ bnd_tile:
   const int sc = tid & 7, sf0 = tid >> 3;
   const int64_t st0 = k0 / GBK;
   // this thread's 16-B chunks of a stage: feature sf0 + FS i of the A1 rows (panel
-  // (GTI/128) bi + f/128) and of the A2 rows (panel bj), samples 2 sc, 2 sc + 1.
+  // pa or pb by f/128) and of the A2 rows (panel bj), samples 2 sc, 2 sc + 1.
   const TA* srcA = CM ? A + ((int64_t)bi * GTI + sf0) * S + k0 + 2 * sc
-                      : A + ((int64_t)bi * (GTI / GT) * S + st0) * GT * GBK + sf0 * GBK + 2 * sc;
+                      : A + ((int64_t)pa * S + st0) * GT * GBK + sf0 * GBK + 2 * sc;
+  const int64_t pd = (int64_t)(pb - pa) * S * GT * GBK;   // from panel pa to panel pb
   // CM with A2: the A2 panels from a second column-major matrix (leading dimension S2; the LU's and
   // the QR's two-operand products, the Cholesky's strip solves), else from A
   const TA* B2 = (CM && A2) ? (const TA*)A2 : A;
@@ -77,13 +101,14 @@ bnd_tile:
   typedef typename pair_of<TA>::type PR;
   PR ra[NA], rb[NB];
   v2d rw, rv;
-  double av[NB];
+  double av[NAV];
 #pragma unroll
-  for (int i = 0; i < NB; ++i) av[i] = 0.0;
+  for (int i = 0; i < NAV; ++i) av[i] = 0.0;
   // fa: std::bool_constant -- the designated tiles of an AV launch run the loop with the Aᵀv
   // products (FA), every other tile the plain loop (no extra loads or VALU)
-  auto gload = [&](int64_t st, auto fa) {
-    constexpr bool FA = decltype(fa)::value;
+  // pt: std::bool_constant -- a pair tile (no A2 loads: its A2 rows are its A1 rows)
+  auto gload = [&](int64_t st, auto fa, auto pt) {
+    constexpr bool FA = decltype(fa)::value, PT = decltype(pt)::value;
     if (PIPE == 3 && st >= 2) return;   // timing build: no global loads after the prologue
     if (CM) {
 #pragma unroll
@@ -95,18 +120,32 @@ bnd_tile:
 #pragma unroll
       for (int i = 0; i < NA; ++i) {
         const int f = FS * i;   // + sf0 (in srcA): the panel of f is f / 128 (FS divides 128)
-        ra[i] = *(const PR*)(srcA + so + (f >> 7) * S * GT * GBK + (f & 127) * GBK);
+        ra[i] = *(const PR*)(srcA + so + (f >> 7) * pd + (f & 127) * GBK);
       }
+      if (!PT) {
 #pragma unroll
-      for (int i = 0; i < NB; ++i) rb[i] = *(const PR*)(srcB + so + FS * GBK * i);
+        for (int i = 0; i < NB; ++i) rb[i] = *(const PR*)(srcB + so + FS * GBK * i);
+      }
     }
     rw = *(const v2d*)(srcW + st * GBK);
     if (FA) rv = *(const v2d*)(srcV + st * GBK);
   };
-  auto swrite = [&](auto fa) {
-    constexpr bool FA = decltype(fa)::value;
+  auto swrite = [&](auto fa, auto pt) {
+    constexpr bool FA = decltype(fa)::value, PT = decltype(pt)::value;
 #pragma unroll
     for (int i = 0; i < NA; ++i) *(v2d*)(la + woff[i]) = widen(ra[i]);
+    if constexpr (PT) {   // lb = the same chunks times w; chunk i is today's rb[i % NB] of its panel
+#pragma unroll
+      for (int i = 0; i < NA; ++i) *(v2d*)(lb + woff[i]) = widen(ra[i]) * rw;
+      if (FA) {
+#pragma unroll
+        for (int i = 0; i < NAV; ++i) {
+          const v2d b = widen(ra[i]);
+          av[i] = __builtin_fma(b[1], rv[1], __builtin_fma(b[0], rv[0], av[i]));
+        }
+      }
+      return;
+    }
 #pragma unroll
     for (int i = 0; i < NB; ++i) *(v2d*)(lb + woff[i]) = widen(rb[i]) * rw;
     if (FA) {
@@ -118,6 +157,8 @@ bnd_tile:
     }
   };
   const int fl = lane & 15, g = lane >> 4, s = swz(fl);
+  // this wave's A2 rows: column half wc of the tile; in a pair tile, of the D block its rows lie in
+  const int brow = wc * 64 + (pair ? (wr >> 1) * GT : 0);
   struct Frag {
     v2d a[NTI], b[4];
   };
@@ -126,7 +167,7 @@ bnd_tile:
 #pragma unroll
     for (int t = 0; t < NTI; ++t) F.a[t] = *(const v2d*)(la + (wr * 64 + 16 * t + fl) * GBK + pc);
 #pragma unroll
-    for (int t = 0; t < 4; ++t) F.b[t] = *(const v2d*)(lb + (wc * 64 + 16 * t + fl) * GBK + pc);
+    for (int t = 0; t < 4; ++t) F.b[t] = *(const v2d*)(lb + (brow + 16 * t + fl) * GBK + pc);
   };
   v4d acc[NTI][4];
 #pragma unroll
@@ -150,11 +191,12 @@ bnd_tile:
   };
   const int nk = (int)((Nk - k0) / GBK);
   Frag F0, F1;
-  auto run = [&](auto fa) {
+  auto run = [&](auto fa, auto pt) {
+    constexpr int NW = decltype(pt)::value ? 2 * NA : NA + NB;   // ds_write_b128 per stage
     if (nk > 0) {
-      gload(0, fa);
-      swrite(fa);
-      if (nk > 1) gload(1, fa);
+      gload(0, fa, pt);
+      swrite(fa, pt);
+      if (nk > 1) gload(1, fa, pt);
       barrier();
       fread(0, F0);
     }
@@ -166,22 +208,29 @@ bnd_tile:
       if (PIPE) {
 #pragma unroll
         for (int i = 0; i < NRD; ++i) {
-          __builtin_amdgcn_sched_group_barrier(0x008, NMM / NRD, 0);   // MFMA
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);           // DS read
+          if (!E1) __builtin_amdgcn_sched_group_barrier(0x008, NMM / NRD, 0);   // MFMA
+          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);                    // DS read
+          if (E1) __builtin_amdgcn_sched_group_barrier(0x008, NMM / NRD, 0);
         }
       }
       barrier();
       // phase 2a
-      if (has1) swrite(fa);
-      if (has2) gload(k + 2, fa);
+      if (has1) swrite(fa, pt);
+      if (has2) gload(k + 2, fa, pt);
       mm(F1, 0, NMM - TAIL);
       if (PIPE) {
         if (has1) {
+          constexpr int HEAD = E2 ? NMM / NRD : 0, Q = (NMM - TAIL - HEAD) / NW;
+          if (E2) {
+            __builtin_amdgcn_sched_group_barrier(0x008, HEAD, 0);   // MFMA
+            __builtin_amdgcn_sched_group_barrier(0x002, 64, 0);     // VALU: all of the phase's
+          }
 #pragma unroll
-          for (int i = 0; i < NA + NB; ++i) {
-            __builtin_amdgcn_sched_group_barrier(0x008, (NMM - TAIL) / (NA + NB), 0);   // MFMA
-            __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);                         // DS write
-            if (has2) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);               // VMEM read
+          for (int i = 0; i < NW; ++i) {
+            if (!E3) __builtin_amdgcn_sched_group_barrier(0x008, Q, 0);    // MFMA
+            __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);             // DS write
+            if (has2) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);   // VMEM read
+            if (E3) __builtin_amdgcn_sched_group_barrier(0x008, Q, 0);
           }
         }
         __builtin_amdgcn_sched_group_barrier(0x008, NMM, 0);
@@ -208,26 +257,37 @@ bnd_tile:
     }
     if (k < nk) body(k, false, false);
   };
-  const bool dav = AV && (int64_t)bj * GT / GTI == bi;   // this tile owns panel bj's Aᵀv rows
-  if constexpr (AV) {
-    if (dav) run(std::true_type{});
-    else run(std::false_type{});
+  // this tile owns panel bj's Aᵀv rows; a pair tile those of both its panels
+  const bool dav = AV && (pair || (int64_t)bj * GT / GTI == bi);
+  if constexpr (PAIRT) {
+    if (pair) run(std::bool_constant<AV>{}, std::true_type{});
+    else if (dav) run(std::bool_constant<AV>{}, std::false_type{});
+    else run(std::false_type{}, std::false_type{});
+  } else if constexpr (AV) {
+    if (dav) run(std::true_type{}, std::false_type{});
+    else run(std::false_type{}, std::false_type{});
   } else {
-    run(std::false_type{});
+    run(std::false_type{}, std::false_type{});
   }
 
   if (dav) {   // lanes 8q .. 8q+7 share a feature
 #pragma unroll
-    for (int i = 0; i < NB; ++i) {
+    for (int i = 0; i < NAV; ++i) {
+      if (i >= NB && !pair) continue;   // chunks NB.. : panel pb of a pair tile (bj = pa there)
       double t = av[i];
       t += __shfl_xor(t, 1);
       t += __shfl_xor(t, 2);
       t += __shfl_xor(t, 4);
-      if (sc == 0) VP[(int64_t)piece * vps + (int64_t)bj * GT + sf0 + FS * i] = t;
+      const int64_t row = i < NB ? (int64_t)bj * GT + sf0 + FS * i : (int64_t)pb * GT + sf0 + FS * (i - NB);
+      if (sc == 0) VP[(int64_t)piece * vps + row] = t;
     }
   }
 
-  // epilogue (the C/D map of gram_f64_kernel): element (il, jl) of the GTI x 128 tile
+  // epilogue (the C/D map of gram_f64_kernel): element (il, jl) of the GTI x 128 tile, at
+  // (grow + il, gcol + jl); the rows of a pair tile go to block (pa, pa) or (pb, pb) by their half
+  const int pw = (wr >> 1) ? pb : pa;
+  const int64_t grow = pair ? (int64_t)(pw - (wr >> 1)) * GT : (int64_t)bi * GTI;
+  const int64_t gcol = pair ? (int64_t)pw * GT : (int64_t)bj * GT;
   if constexpr (BND || CM) {   // the persistent and gen-form launches: old values loaded ahead of the stores
 #pragma unroll
     for (int ti = 0; ti < NTI; ++ti)
@@ -247,8 +307,8 @@ bnd_tile:
             continue;
           }
           if (packed) dst = G + ((int64_t)tix * (GTI / GT) + il / GT) * GT * GT + jl * GT + (il % GT);
-          else if (upper) dst = G + ((int64_t)bi * GTI + il) * ldg + (int64_t)bj * GT + jl;
-          else dst = G + ((int64_t)bj * GT + jl) * ldg + (int64_t)bi * GTI + il;
+          else if (upper) dst = G + (grow + il) * ldg + gcol + jl;
+          else dst = G + (gcol + jl) * ldg + grow + il;
           if (accumulate) *dst += acc[ti][tj][r];
           else *dst = acc[ti][tj][r];
         }

@@ -25,6 +25,10 @@ struct ProxArgsH {
 // ---- gram.hip
 void gram_tile_list(int nb, int2* out, int* ntiles);
 void gram_tile_list_tall(int nb, int2* out, int* ntiles);
+// the diagonal's D1 blocks two to a tile (gram_tiles.h); only the unpacked launches of the
+// interleaved 256 x 128 kernels (gram_pair_ok) take such a list
+void gram_tile_list_tall_paired(int nb, int2* out, int* ntiles);
+int gram_pair_ok();
 // Main Gram on the panel-blocked A (lda = S = Npad / 16); `packed` bit 0 = packed slots (else the
 // upper triangle), bit 1 = accumulate into G.  tall = 1: 256 x 128 tiles from
 // gram_tile_list_tall (nb even); packed slots are then the 128 x 128 halves (2t, 2t+1) of

@@ -226,6 +226,14 @@ struct scs_ctx {
   int4* gcomb = nullptr;
   int gseglen = 0, gncomb = 0, gnsplit = 1;
   double* gpart = nullptr;
+  // the unpacked launches' list and schedule with the diagonal's D1 blocks paired (gram_tiles.h;
+  // null without pairing: SCS_GRAM_DIAGPAIR=0, 128 x 128 tiles, a non-interleaved kernel).  The packed
+  // launches (slot = list index) and the strip lists keep `tiles`.
+  int2* ptiles = nullptr;
+  int nptiles = 0;
+  int4* pwork = nullptr;
+  int4* pcomb = nullptr;
+  int pseglen = 0, pncomb = 0, pnsplit = 1;
   double* vpart = nullptr;   // fused Aᵀv partials: max(gnsplit, strip nsplits, 1) rows of mpad
   // strip pipeline (gram_factor_pipelined): the Gram's tile list cut into the factor's outer
   // strips (tiles with bj in strip s), one tail-balanced schedule each; the factor stream and
@@ -721,11 +729,21 @@ void ensure_gram(scs_ctx* c) {
   HCK(hipMemcpyAsync(c->tiles, tl.data(), sizeof(int2) * nt, hipMemcpyHostToDevice, c->st));
   c->ntiles = nt;
   c->nslots = (int)ul.size();
+  std::vector<int2> tp;
+  if (c->tall && gram_pair_ok()) {
+    int np = 0;
+    tp.resize(tl.size());
+    gram_tile_list_tall_paired(nb, tp.data(), &np);
+    tp.resize(np);
+    c->ptiles = dalloc<int2>(c, np);
+    HCK(hipMemcpyAsync(c->ptiles, tp.data(), sizeof(int2) * np, hipMemcpyHostToDevice, c->st));
+    c->nptiles = np;
+  }
   {
     const char* ev = std::getenv("SCS_GRAM_SCHED");
     if (!(ev && ev[0] == '0')) {
       std::vector<int4> wk, cb;
-      int npart = 0;
+      int npart = 0, npartp = 0;
       // the AV launches' designated tiles first in each XCD's order on 256 x 128 tiles (C3 Gram
       // 3863.7 -> 3846.6 ms); on 128 x 128 tiles it measured slower (C2 Gram +0.3 ms unfused, +0.9 fused;
       // profiles/r05/diagfirst/).  SCS_GRAM_DIAGFIRST=0 / 1: off / also on 128 x 128 tiles (A/B)
@@ -738,15 +756,26 @@ void ensure_gram(scs_ctx* c) {
       if (c->gncomb > 0) {
         c->gcomb = dalloc<int4>(c, cb.size());
         HCK(hipMemcpyAsync(c->gcomb, cb.data(), sizeof(int4) * cb.size(), hipMemcpyHostToDevice, c->st));
-        c->gpart = dalloc<double>(c, (size_t)npart * (c->tall ? 256 : 128) * 128);
       }
+      if (c->ptiles) {   // the same rule on the paired list (its tail, and so its K-split tiles, differ)
+        c->pseglen = gram_schedule(tp.data(), c->nptiles, 32, wk, cb, &c->pnsplit, &npartp, dfg);
+        c->pncomb = (int)cb.size();
+        c->pwork = dalloc<int4>(c, wk.size());
+        HCK(hipMemcpyAsync(c->pwork, wk.data(), sizeof(int4) * wk.size(), hipMemcpyHostToDevice, c->st));
+        if (c->pncomb > 0) {
+          c->pcomb = dalloc<int4>(c, cb.size());
+          HCK(hipMemcpyAsync(c->pcomb, cb.data(), sizeof(int4) * cb.size(), hipMemcpyHostToDevice, c->st));
+        }
+      }
+      if (std::max(npart, npartp) > 0)
+        c->gpart = dalloc<double>(c, (size_t)std::max(npart, npartp) * (c->tall ? 256 : 128) * 128);
     }
   }
   {
     // the strips of the pipeline: tiles whose column block (bj, 128-wide) lies in outer strip s
     const int OB = chol_outer_block(), ns = (nb + OB - 1) / OB;
     c->gstrip.assign(ns, scs_ctx::GStrip());
-    c->vpieces = std::max(c->gnsplit, 1);
+    c->vpieces = std::max(std::max(c->gnsplit, c->pnsplit), 1);
     int npart_max = 0;
     for (int s2 = 0; s2 < ns; ++s2) {
       std::vector<int2> st;
@@ -1830,11 +1859,14 @@ void gram_main_stream(scs_ctx* c, const double* w, double* out, int packed) {
     c->ring_n[s] = n;
     const int mode = packed | (k > 0 ? 2 : 0);
     const int64_t nk = round_up(std::max<int64_t>(n, 1), 16);   // w + r0 + nk <= w + Npad
+    const bool pr = c->ptiles && !(packed & 1);   // unpacked: the paired list
     if (c->gwork)
-      HCK(gram_launch_sched(slot, 0, R / 16, w + r0, nk, c->gwork, c->gseglen, c->gnsplit, c->gcomb, c->gncomb, c->gpart,
-                            out, c->mpad, mode, c->tall, c->st));
+      HCK(gram_launch_sched(slot, 0, R / 16, w + r0, nk, pr ? c->pwork : c->gwork, pr ? c->pseglen : c->gseglen,
+                            pr ? c->pnsplit : c->gnsplit, pr ? c->pcomb : c->gcomb, pr ? c->pncomb : c->gncomb,
+                            c->gpart, out, c->mpad, mode, c->tall, c->st));
     else
-      HCK(gram_launch(slot, 0, R / 16, w + r0, nk, c->tiles, c->ntiles, out, c->mpad, mode, c->tall, c->st));
+      HCK(gram_launch(slot, 0, R / 16, w + r0, nk, pr ? c->ptiles : c->tiles, pr ? c->nptiles : c->ntiles, out,
+                      c->mpad, mode, c->tall, c->st));
     c->gram_kname = gram_main_kernel_name();
   }
 }
@@ -1853,14 +1885,17 @@ void gram_main(scs_ctx* c, const double* w, double* out, int packed, const doubl
     return;
   }
   const double* A = dense_A(c);
-  const int npiece = (v && c->gwork) ? std::max(c->gnsplit, 1) : 1;
+  const bool pr = c->ptiles && !(packed & 1);   // unpacked: the paired list
+  const int nsplit = pr ? c->pnsplit : c->gnsplit;
+  const int npiece = (v && c->gwork) ? std::max(nsplit, 1) : 1;
   if (v && npiece > 1) HCK(hipMemsetAsync(c->vpart, 0, sizeof(double) * npiece * c->mpad, c->st));
   if (c->gwork)
-    HCK(gram_launch_sched(A, dense_a32(c), c->nstage, w, c->Npad, c->gwork, c->gseglen, c->gnsplit, c->gcomb, c->gncomb,
+    HCK(gram_launch_sched(A, dense_a32(c), c->nstage, w, c->Npad, pr ? c->pwork : c->gwork,
+                          pr ? c->pseglen : c->gseglen, nsplit, pr ? c->pcomb : c->gcomb, pr ? c->pncomb : c->gncomb,
                           c->gpart, out, c->mpad, packed, c->tall, c->st, v, c->vpart, c->mpad));
   else
-    HCK(gram_launch(A, dense_a32(c), c->nstage, w, c->Npad, c->tiles, c->ntiles, out, c->mpad, packed, c->tall, c->st,
-                    v, c->vpart, c->mpad));
+    HCK(gram_launch(A, dense_a32(c), c->nstage, w, c->Npad, pr ? c->ptiles : c->tiles, pr ? c->nptiles : c->ntiles,
+                    out, c->mpad, packed, c->tall, c->st, v, c->vpart, c->mpad));
   c->gram_kname = gram_main_kernel_name();
   if (v) HCK(gram_vfinal_launch(c->vpart, npiece, c->mpad, c->m, vout, c->st));
 }
@@ -2694,6 +2729,11 @@ static void reset_data(scs_ctx* c) {
   c->nstiles = 0;
   dfree_t(c, c->gwork);
   dfree_t(c, c->gcomb);
+  dfree_t(c, c->ptiles);
+  dfree_t(c, c->pwork);
+  dfree_t(c, c->pcomb);
+  c->nptiles = c->pseglen = c->pncomb = 0;
+  c->pnsplit = 1;
   dfree_t(c, c->gpart);
   dfree_t(c, c->vpart);
   for (auto& g : c->gstrip) {

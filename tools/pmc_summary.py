@@ -12,7 +12,8 @@ import json
 import os
 
 # the main-Gram kernels (their rocprofv3 names: every template argument, defaults included)
-KERNELS = ("gram_sia_kernel<1, 4, false, true, false>", "gram_sia_kernel<1, 2, false, true, false>",
+KERNELS = ("gram_sia_kernel<10, 4, false, true, false>", "gram_sia_kernel<10, 4, false, false, false>",
+           "gram_sia_kernel<1, 4, false, true, false>", "gram_sia_kernel<1, 2, false, true, false>",
            "gram_sia_kernel<1, 4, false, false, false>", "gram_sia_kernel<1, 2, false, false, false>",
            "gram_sia_kernel<1, 4, false, true>", "gram_sia_kernel<1, 4>", "gram_sia_kernel<1, 2>",
            "gram_sia_kernel<1, 2, false, false>", "gram_sia_kernel<1, 4, false, false>", "gram_glds_kernel",
