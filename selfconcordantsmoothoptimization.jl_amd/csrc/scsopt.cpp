@@ -2284,6 +2284,19 @@ struct CbScope {
   }
 };
 
+// The Hessians written straight into G (Rosenbrock, a callback's hess_fx, the quadratic loss) fill
+// its leading m x m block only and rely on the padded rows / columns being block-diag(H, I).  A
+// Cholesky that met a non-positive pivot (an indefinite system: the LU then solves the copy) runs on
+// through NaN pivots and leaves NaN in the padded columns of the rows it touched, which the next
+// step's factor and LU would carry into every entry of the direction: clear the padding first (a
+// Gram launch rewrites all of G, so the data losses never saw this).
+static void clear_gram_padding(scs_ctx* c) {
+  const int64_t m = c->m, ld = c->mpad;
+  if (ld == m) return;
+  HCK(hipMemsetAsync(c->G + m * ld, 0, sizeof(double) * (size_t)(ld - m) * ld, c->st));   // columns >= m
+  HCK(hipMemset2DAsync(c->G + m, sizeof(double) * ld, 0, sizeof(double) * (ld - m), m, c->st));   // rows >= m
+}
+
 // ProxNSCORE / ProxGGNSCORE step
 void step_newton(scs_ctx* c, const double* xh, int64_t iter, double* x_new, double* dx, double* pri) {
   const int64_t m = c->m;
@@ -2305,18 +2318,21 @@ void step_newton(scs_ctx* c, const double* xh, int64_t iter, double* x_new, doub
   if (c->method == SCS_PROX_NSCORE) {
     // H = hess_fx, ∇q = grad_fx + λ gr  (prox-N-SCORE.jl:183-204)
     if (c->loss == SCS_LOSS_ROSENBROCK) {
+      clear_gram_padding(c);
       HCK(launch_rosen(c->x, m, 2, nullptr, c->G, c->mpad, c->st));
       HCK(launch_rosen(c->x, m, 1, c->gtmp, nullptr, 0, c->st));
     } else if (c->loss == SCS_LOSS_CALLBACK) {
       // H = hess_fx(x) (m x m, column-major) into the leading block of G; the padded rows /
-      // columns keep block-diag(H, I) (zero from the allocation, the padded diagonal set by
-      // chol_factor)
+      // columns keep block-diag(H, I) (zero from the allocation and clear_gram_padding, the padded
+      // diagonal set by chol_factor)
       const double* H = cb_eval(c, SCS_CB_HESS, xh, c->x, (size_t)m * m);
+      clear_gram_padding(c);
       HCK(hipMemcpy2DAsync(c->G, sizeof(double) * c->mpad, H, sizeof(double) * m, sizeof(double) * m, m,
                            hipMemcpyHostToDevice, c->st));
       grad_f_dev(c, xh, c->x, c->gtmp);
     } else if (c->loss == SCS_LOSS_QUADRATIC) {
       require_dense(c, "the quadratic loss");
+      clear_gram_padding(c);
       HCK(launch_half_sym(c->A, c->nstage, m, c->G, c->mpad, c->st));   // fp64 A only (require_dense)
       grad_f_dev(c, xh, c->x, c->gtmp);
     } else {
