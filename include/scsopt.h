@@ -325,6 +325,46 @@ int scs_gen_sparse(scs_ctx* ctx, const scs_synth* spec, int val_f32);
 int scs_get_nnz(scs_ctx* ctx, int64_t* nnz);
 /* CSR copy back to the host (values widened to fp64).                       */
 int scs_get_sparse(scs_ctx* ctx, int64_t* rowptr, int32_t* colidx, double* val);
+/* The CSC copy back to the host, as scs_get_sparse returns the CSR one: m + 1 column pointers,
+ * nnz row indices and values (widened), rows ascending within a column.                        */
+int scs_get_sparse_csc(scs_ctx* ctx, int64_t* colptr, int32_t* rowidx, double* valT);
+/* ---- a sparse A that is already on the device  (torch.sparse_csr_tensor, a CuPy csr_matrix, a
+ * triple of ROCArrays).  A CSR is all the caller supplies: d_rowptr (N + 1 entries of ptr_bytes = 4,
+ * int32, or 8, int64), d_colidx (nnz entries of idx_bytes = 4 or 8, 0-based) and d_val (nnz entries
+ * of val_bytes = 4, float, or 8, double), device memory on the context's device.  All pointer x index
+ * widths are legal, and val_f32 alone decides the stored type (a double source with val_f32 = 1 is
+ * rounded to nearest even, a float source with val_f32 = 0 widened).  With nnz = 0, d_colidx and
+ * d_val may be NULL.  One pass reads the source, validates it and writes the context's CSR; the CSC
+ * copy is built on the device from the row-sorted CSR (an integer counting pass over runs of equal
+ * column indices, a scan, a placing pass, and the per-column sort the host door runs too).  Column
+ * indices may be unsorted within a row and (row, column) pairs may repeat: duplicates are kept, not
+ * summed, in storage order.  After the call the context holds, bit for bit, what scs_set_sparse
+ * holds from the same CSR arrays and their stable transposition (scipy's tocsr -> tocsc), whatever
+ * the order in which the device's waves arrived.  Peak device memory is the host door's plus the
+ * source; until the validation has passed, the earlier data is kept as well.
+ * y and src_stream are scs_set_data_device's: y (N doubles) may be a host or a device pointer;
+ * src_stream is NULL, (void*)1, (void*)2 or the producer's stream; the call returns with the
+ * context's stream synchronised, so the source may be freed on return.
+ * Refused with SCS_ERR_ARG, before anything of the context is freed: ptr_bytes / idx_bytes /
+ * val_bytes other than 4 or 8; a NULL d_rowptr, or a NULL d_colidx / d_val with nnz > 0; a pointer
+ * that hipPointerGetAttributes does not report as device memory of the context's device; an array
+ * that runs past its allocation (hipMemGetAddressRange); rowptr[0] != 0, rowptr[N] != nnz or a
+ * decreasing rowptr (the message names the first offending row); a column index outside [0, m),
+ * compared in the source width (the message names the first offending position); nnz above
+ * 2^32 - 1 (the sorts count their items in 32 unsigned bits; scs_set_sparse's INT32_MAX * 64 lies
+ * above that and is refused a fortiori); a multi-device context.  The validation runs on the device and never reads outside
+ * the source arrays, whatever they hold.                                                          */
+int scs_set_sparse_device(scs_ctx* ctx, int64_t N, int64_t m, int64_t nnz,
+                          const void* d_rowptr, int ptr_bytes, const void* d_colidx, int idx_bytes,
+                          const void* d_val, int val_bytes, int val_f32, const double* y,
+                          void* src_stream, int64_t N_global, int64_t row0);
+/* CSR held-out rows from the device (N x the data's m), as scs_set_sparse_device takes them; the
+ * arrays and y are both required.  No CSC copy is built, as for scs_set_test_sparse.  A refusal
+ * leaves an earlier held-out set in place.                                                       */
+int scs_set_test_sparse_device(scs_ctx* ctx, int64_t N, int64_t nnz,
+                               const void* d_rowptr, int ptr_bytes, const void* d_colidx, int idx_bytes,
+                               const void* d_val, int val_bytes, int val_f32, const double* y,
+                               void* src_stream, int64_t N_global, int64_t row0);
 
 /* ---- problem / regularizer / smoother ----------------------------------- */
 int scs_set_loss(scs_ctx* ctx, int loss_kind, int ggn_kind, double scale);

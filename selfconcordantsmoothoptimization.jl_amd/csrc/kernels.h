@@ -425,6 +425,18 @@ hipError_t blk_pad(int64_t* cnt, int64_t n, int f32, hipStream_t st);
 hipError_t blk_scan(void* temp, size_t* temp_bytes, const int64_t* cnt, int64_t* bptr, int64_t n, hipStream_t st);
 hipError_t blk_scatter(const int64_t* ptr, const int* idx, const void* val, int f32, int64_t nrows, int shift,
                        const int64_t* bptr, const int64_t* first, uint16_t* lidx, void* bval, hipStream_t st);
+// A device CSR (scs_set_sparse_device).  csr_ingest: rowptr (ptr_bytes 4 / 8), colidx (idx_bytes 4 / 8)
+// and val (val_bytes 4 / 8) -> optr (int64), oidx (int32), oval (f32: float, else double), validated in
+// the same pass; rec[0] = min over faulty rows of 4·row + kind (0: rowptr[0] != 0, 1: not monotone,
+// 2: rowptr[N] != nnz), rec[1] = first position with an index outside [0, m); the caller sets both
+// to all ones.  csr_claim / csr_place: the transposition of a row-sorted CSR around blk_scan (cnt:
+// ncols + 1 zeroed counters; rank: nnz entries of 32 bits, so nnz < 2^32).
+hipError_t csr_ingest(const void* rowptr, int ptr_bytes, const void* colidx, int idx_bytes, const void* val,
+                      int val_bytes, int64_t N, int64_t m, int64_t nnz, int64_t* optr, int* oidx, void* oval,
+                      int f32, unsigned long long* rec, hipStream_t st);
+hipError_t csr_claim(const int64_t* ptr, const int* idx, int64_t nrows, int64_t* cnt, uint32_t* rank, hipStream_t st);
+hipError_t csr_place(const int64_t* ptr, const int* idx, const void* val, int f32, int64_t nrows,
+                     const int64_t* colptr, const uint32_t* rank, int* rowidx, void* valT, hipStream_t st);
 // sparse Gram G = Aᵀ diag(w) A (upper part, column j up to the end of its diagonal tile) from the
 // CSC copy and a Gram-blocked CSR copy (block width 2^shift, unpadded segments): Σ_r nnz_r² work
 int sparse_gram_shift();

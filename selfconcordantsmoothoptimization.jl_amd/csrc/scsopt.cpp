@@ -2852,30 +2852,41 @@ static void check_device_src(scs_ctx* c, const DenseSrc& s, int64_t N, int64_t m
   }
 }
 
+// The context's stream waits for the work queued so far on the producer's stream of a device source
+// (the dense and the sparse device door).
+static void join_src_stream(scs_ctx* c, hipStream_t src_stream) {
+  // __cuda_array_interface__'s two small integers are no handles, and a runtime that does not know
+  // hipStreamLegacy reads (hipStream_t)1 as an object: neither value ever reaches the runtime as one.
+  // 1, the legacy default stream, is the NULL stream; 2, the caller's per-thread default stream, is
+  // covered by a device-wide synchronise.
+  const uintptr_t sv = (uintptr_t)src_stream;
+  if (sv == 2) {
+    HCK(hipDeviceSynchronize());
+  } else if (sv) {   // the work queued on the producer's stream so far
+    hipEvent_t ev;
+    HCK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    hipError_t e = hipEventRecord(ev, sv == 1 ? (hipStream_t) nullptr : src_stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(c->st, ev, 0);
+    (void)hipEventDestroy(ev);
+    HCK(e);
+  }
+}
+
+// y of a device door: a host or a device pointer (the library asks the pointer's attributes)
+static void copy_y_any(scs_ctx* c, const double* y, int64_t N) {
+  if (!y || N <= 0) return;
+  const bool ydev = is_device_ptr(y, nullptr);
+  HCK(hipMemcpyAsync(c->y, y, sizeof(double) * N, ydev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->st));
+}
+
 // N rows of src -> the context's (current view's) A and y.  Host rows: panel by panel through the
 // column-major staging buffer.  Device rows: one re-tile pass that writes the whole block, padding
 // included.  Ends with the stream drained: the caller may free the source.
 static void load_dense(scs_ctx* c, const DenseSrc& s, int64_t N, const double* y) {
   if (s.dev) {
-    // __cuda_array_interface__'s two small integers are no handles, and a runtime that does not know
-    // hipStreamLegacy reads (hipStream_t)1 as an object: neither value ever reaches the runtime as one.
-    // 1, the legacy default stream, is the NULL stream; 2, the caller's per-thread default stream, is
-    // covered by a device-wide synchronise.
-    const uintptr_t sv = (uintptr_t)s.src_stream;
-    if (sv == 2) {
-      HCK(hipDeviceSynchronize());
-    } else if (sv) {   // the work queued on the producer's stream so far
-      hipEvent_t ev;
-      HCK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-      hipError_t e = hipEventRecord(ev, sv == 1 ? (hipStream_t) nullptr : s.src_stream);
-      if (e == hipSuccess) e = hipStreamWaitEvent(c->st, ev, 0);
-      (void)hipEventDestroy(ev);
-      HCK(e);
-    }
-    const bool ydev = y && is_device_ptr(y, nullptr);
+    join_src_stream(c, s.src_stream);
     HCK(launch_tile_device(s.A, s.in32, s.sn, s.sm, N, c->m, c->Npad, c->mpad, c->A, c->a32, c->st));
-    if (y && N > 0)
-      HCK(hipMemcpyAsync(c->y, y, sizeof(double) * N, ydev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->st));
+    copy_y_any(c, y, N);
     sync(c);
     return;
   }
@@ -3119,6 +3130,49 @@ static void build_blocked(scs_ctx* c, int64_t nrows, int64_t ncols, int64_t* ptr
   dfree_t(c, first);
 }
 
+// The CSC copy from the row-sorted CSR (after build_blocked on it), for a source that brings none
+// (scs_set_sparse_device): claim, scan, place (sparse.hip).  Columns come out in arrival order of
+// their runs; the stable sort of build_blocked on the CSC copy makes the order the host door's.
+static void transpose_csr(scs_ctx* c) {
+  const int64_t N = c->N, m = c->m, nnz = c->nnz;
+  c->colptr = dalloc<int64_t>(c, m + 1);
+  c->rowidx = dalloc<int>(c, nnz, false);
+  c->valT = c->sp_f32 ? (void*)dalloc<float>(c, (size_t)nnz, false) : (void*)dalloc<double>(c, (size_t)nnz, false);
+  if (nnz <= 0 || N <= 0) return;
+  int64_t* cnt = dalloc<int64_t>(c, m + 1);
+  uint32_t* rank = dalloc<uint32_t>(c, (size_t)nnz, false);   // nnz < 2^32 (check_sparse_src)
+  HCK(csr_claim(c->rowptr, c->colidx, N, cnt, rank, c->st));
+  size_t tb = 0;
+  HCK(blk_scan(nullptr, &tb, cnt, c->colptr, m + 1, c->st));
+  void* tmp = dalloc<char>(c, tb);
+  HCK(blk_scan(tmp, &tb, cnt, c->colptr, m + 1, c->st));
+  HCK(csr_place(c->rowptr, c->colidx, c->val, c->sp_f32, N, c->colptr, rank, c->rowidx, c->valT, c->st));
+  sync(c);
+  dfree(c, tmp);
+  dfree_t(c, rank);
+  dfree_t(c, cnt);
+}
+
+// what scs_set_sparse and scs_set_sparse_device share once rowptr / colidx / val (and, from the host,
+// colptr / rowidx / valT) and y are in place
+static void finish_sparse(scs_ctx* c, bool transpose) {
+  build_blocked(c, c->N, c->m, c->rowptr, c->colidx, c->val, c->bcsr);
+  if (transpose) transpose_csr(c);
+  build_blocked(c, c->m, c->N, c->colptr, c->rowidx, c->valT, c->bcsc);
+  alloc_mspace(c);
+  alloc_nspace(c);
+  sync(c);
+  c->has_data = true;
+}
+
+// the held-out counterpart: CSR only
+static void finish_sparse_test(scs_ctx* c, int64_t N) {
+  build_blocked(c, N, c->m, c->rowptr, c->colidx, c->val, c->bcsr);
+  alloc_nspace(c);
+  sync(c);
+  c->tset.on = true;
+}
+
 int scs_set_sparse(scs_ctx* c, int64_t N, int64_t m, int64_t nnz, const int64_t* rowptr, const int32_t* colidx,
                    const double* val, const int64_t* colptr, const int32_t* rowidx, const double* valT, int f32,
                    const double* y, int64_t Nglob, int64_t row0) {
@@ -3158,12 +3212,130 @@ int scs_set_sparse(scs_ctx* c, int64_t N, int64_t m, int64_t nnz, const int64_t*
     }
     c->y = dalloc<double>(c, c->Npad);
     if (y && N > 0) h2d(c, c->y, y, N);
-    build_blocked(c, N, m, c->rowptr, c->colidx, c->val, c->bcsr);
-    build_blocked(c, m, N, c->colptr, c->rowidx, c->valT, c->bcsc);
-    alloc_mspace(c);
-    alloc_nspace(c);
-    sync(c);
-    c->has_data = true;
+    finish_sparse(c, false);
+  });
+}
+
+// ---- a CSR that is already on the device (scs_set_sparse_device / scs_set_test_sparse_device) -------
+struct SparseSrc {
+  const void* ptr;
+  int ptr_bytes;
+  const void* idx;
+  int idx_bytes;
+  const void* val;
+  int val_bytes;
+  hipStream_t src_stream;
+  const char* what;   // the entry point, for messages
+};
+
+// one source array: device memory on the context's device, inside its allocation (where the runtime can tell)
+static void check_device_array(scs_ctx* c, const char* what, const char* name, const void* p, int64_t n, int eb) {
+  int dev = -1;
+  if (!is_device_ptr(p, &dev))
+    fail(c, SCS_ERR_ARG, "%s: %s is not device memory (hipPointerGetAttributes); host arrays go through "
+                         "scs_set_sparse", what, name);
+  if (dev != c->dev) fail(c, SCS_ERR_ARG, "%s: %s lives on device %d, the context on device %d", what, name, dev, c->dev);
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) == hipSuccess) {
+    if ((const char*)p + (size_t)n * eb > (const char*)base + size)
+      fail(c, SCS_ERR_ARG, "%s: %s (%lld entries of %d bytes) runs past the end of its allocation", what, name,
+           (long long)n, eb);
+  } else {
+    (void)hipGetLastError();
+  }
+}
+
+// the host-side refusals of a device CSR, all before anything is queued or freed
+static void check_sparse_src(scs_ctx* c, const SparseSrc& s, int64_t N, int64_t m, int64_t nnz) {
+  const char* what = s.what;
+  if (s.ptr_bytes != 4 && s.ptr_bytes != 8)
+    fail(c, SCS_ERR_ARG, "%s: ptr_bytes = %d (8: int64, 4: int32)", what, s.ptr_bytes);
+  if (s.idx_bytes != 4 && s.idx_bytes != 8)
+    fail(c, SCS_ERR_ARG, "%s: idx_bytes = %d (8: int64, 4: int32)", what, s.idx_bytes);
+  if (s.val_bytes != 4 && s.val_bytes != 8)
+    fail(c, SCS_ERR_ARG, "%s: val_bytes = %d (8: double, 4: float)", what, s.val_bytes);
+  if (N < 0 || N > INT32_MAX || m <= 0 || m > INT32_MAX || nnz < 0)   // both index copies are int32
+    fail(c, SCS_ERR_ARG, "%s: bad dimensions N=%lld m=%lld nnz=%lld", what, (long long)N, (long long)m, (long long)nnz);
+  // the host door's limit is INT32_MAX * 64; the segmented sort both doors run counts its items in 32
+  // unsigned bits, and this door does not hand it more
+  if (nnz > (int64_t)UINT32_MAX)
+    fail(c, SCS_ERR_ARG, "%s: nnz too large (%lld: the per-row and per-column sorts take at most 2^32 - 1 entries)",
+         what, (long long)nnz);
+  if (!s.ptr) fail(c, SCS_ERR_ARG, "%s: d_rowptr is NULL", what);
+  if (nnz > 0 && !s.idx) fail(c, SCS_ERR_ARG, "%s: d_colidx is NULL with nnz = %lld", what, (long long)nnz);
+  if (nnz > 0 && !s.val) fail(c, SCS_ERR_ARG, "%s: d_val is NULL with nnz = %lld", what, (long long)nnz);
+  check_device_array(c, what, "d_rowptr", s.ptr, N + 1, s.ptr_bytes);
+  if (nnz > 0) {
+    check_device_array(c, what, "d_colidx", s.idx, nnz, s.idx_bytes);
+    check_device_array(c, what, "d_val", s.val, nnz, s.val_bytes);
+  }
+}
+
+// The source -> fresh rowptr (int64) / colidx (int32) / val (stored type) buffers, validated on the
+// device in the same pass (sparse.hip csr_ingest) and read back as one small record.  The context
+// itself is untouched: a refusal frees the buffers and leaves the earlier data usable.
+struct CsrBufs {
+  int64_t* rowptr = nullptr;
+  int* colidx = nullptr;
+  void* val = nullptr;
+};
+
+static CsrBufs ingest_csr(scs_ctx* c, const SparseSrc& s, int64_t N, int64_t m, int64_t nnz, int f32) {
+  join_src_stream(c, s.src_stream);
+  CsrBufs b;
+  b.rowptr = dalloc<int64_t>(c, N + 1, false);
+  b.colidx = dalloc<int>(c, nnz, false);
+  b.val = f32 ? (void*)dalloc<float>(c, (size_t)nnz, false) : (void*)dalloc<double>(c, (size_t)nnz, false);
+  unsigned long long* drec = dalloc<unsigned long long>(c, 2, false);
+  unsigned long long rec[2] = {0, 0};
+  HCK(hipMemsetAsync(drec, 0xFF, sizeof(rec), c->st));
+  HCK(csr_ingest(s.ptr, s.ptr_bytes, s.idx, s.idx_bytes, s.val, s.val_bytes, N, m, nnz, b.rowptr, b.colidx, b.val,
+                 f32, drec, c->st));
+  HCK(hipMemcpyAsync(rec, drec, sizeof(rec), hipMemcpyDeviceToHost, c->st));
+  sync(c);
+  dfree_t(c, drec);
+  if (rec[0] != ~0ull || rec[1] != ~0ull) {
+    dfree_t(c, b.rowptr);
+    dfree_t(c, b.colidx);
+    dfree(c, b.val);
+    if (rec[0] != ~0ull) {
+      const long long row = (long long)(rec[0] >> 2);
+      switch ((int)(rec[0] & 3)) {
+        case 0: fail(c, SCS_ERR_ARG, "%s: rowptr must start at 0 (row %lld)", s.what, row);
+        case 1: fail(c, SCS_ERR_ARG, "%s: rowptr not monotone at row %lld", s.what, row);
+        default: fail(c, SCS_ERR_ARG, "%s: rowptr must end at nnz = %lld (row %lld)", s.what, (long long)nnz, row);
+      }
+    }
+    fail(c, SCS_ERR_ARG, "%s: column index outside [0, %lld) at position %lld", s.what, (long long)m,
+         (long long)rec[1]);
+  }
+  return b;
+}
+
+int scs_set_sparse_device(scs_ctx* c, int64_t N, int64_t m, int64_t nnz, const void* d_rowptr, int ptr_bytes,
+                          const void* d_colidx, int idx_bytes, const void* d_val, int val_bytes, int f32,
+                          const double* y, void* src_stream, int64_t Nglob, int64_t row0) {
+  if (!c) return SCS_ERR_ARG;
+  const SparseSrc s{d_rowptr, ptr_bytes, d_colidx, idx_bytes, d_val, val_bytes, (hipStream_t)src_stream,
+                    "scs_set_sparse_device"};
+  if (is_group(c)) return refuse_group_device(c, s.what);
+  return guarded(c, [&] {
+    HCK(hipSetDevice(c->dev));
+    check_sparse_src(c, s, N, m, nnz);
+    const CsrBufs b = ingest_csr(c, s, N, m, nnz, f32 ? 1 : 0);
+    reset_data(c);
+    set_dims(c, N, m, Nglob, row0);
+    c->generic = false;
+    c->sparse = true;
+    c->sp_f32 = f32 ? 1 : 0;
+    c->nnz = nnz;
+    c->rowptr = b.rowptr;
+    c->colidx = b.colidx;
+    c->val = b.val;
+    c->y = dalloc<double>(c, c->Npad);
+    copy_y_any(c, y, N);
+    finish_sparse(c, true);
   });
 }
 
@@ -3221,24 +3393,31 @@ int scs_get_nnz(scs_ctx* c, int64_t* nnz) {
   });
 }
 
-int scs_get_sparse(scs_ctx* c, int64_t* rowptr, int32_t* colidx, double* val) {
-  return guarded(c, [&] {
-    if (!c->has_data || !c->sparse) fail(c, SCS_ERR_STATE, "no sparse data");
-    if (rowptr) HCK(hipMemcpyAsync(rowptr, c->rowptr, sizeof(int64_t) * (c->N + 1), hipMemcpyDeviceToHost, c->st));
-    if (colidx && c->nnz)
-      HCK(hipMemcpyAsync(colidx, c->colidx, sizeof(int) * c->nnz, hipMemcpyDeviceToHost, c->st));
-    if (val && c->nnz) {
-      if (c->sp_f32) {
-        std::vector<float> h((size_t)c->nnz);
-        HCK(hipMemcpyAsync(h.data(), c->val, sizeof(float) * c->nnz, hipMemcpyDeviceToHost, c->st));
-        sync(c);
-        for (int64_t p = 0; p < c->nnz; ++p) val[p] = h[p];
-      } else {
-        HCK(hipMemcpyAsync(val, c->val, sizeof(double) * c->nnz, hipMemcpyDeviceToHost, c->st));
-      }
+// one compressed copy (nseg + 1 pointers, nnz indices and values) back to the host, values widened
+static void get_compressed(scs_ctx* c, int64_t nseg, const int64_t* dptr, const int* didx, const void* dval,
+                           int64_t* ptr, int32_t* idx, double* val) {
+  if (!c->has_data || !c->sparse) fail(c, SCS_ERR_STATE, "no sparse data");
+  if (ptr) HCK(hipMemcpyAsync(ptr, dptr, sizeof(int64_t) * (nseg + 1), hipMemcpyDeviceToHost, c->st));
+  if (idx && c->nnz) HCK(hipMemcpyAsync(idx, didx, sizeof(int) * c->nnz, hipMemcpyDeviceToHost, c->st));
+  if (val && c->nnz) {
+    if (c->sp_f32) {
+      std::vector<float> h((size_t)c->nnz);
+      HCK(hipMemcpyAsync(h.data(), dval, sizeof(float) * c->nnz, hipMemcpyDeviceToHost, c->st));
+      sync(c);
+      for (int64_t p = 0; p < c->nnz; ++p) val[p] = h[p];
+    } else {
+      HCK(hipMemcpyAsync(val, dval, sizeof(double) * c->nnz, hipMemcpyDeviceToHost, c->st));
     }
-    sync(c);
-  });
+  }
+  sync(c);
+}
+
+int scs_get_sparse(scs_ctx* c, int64_t* rowptr, int32_t* colidx, double* val) {
+  return guarded(c, [&] { get_compressed(c, c->N, c->rowptr, c->colidx, c->val, rowptr, colidx, val); });
+}
+
+int scs_get_sparse_csc(scs_ctx* c, int64_t* colptr, int32_t* rowidx, double* valT) {
+  return guarded(c, [&] { get_compressed(c, c->m, c->colptr, c->rowidx, c->valT, colptr, rowidx, valT); });
 }
 
 // ---- held-out data (Problem(...; Atest, ytest), problems.jl:27-28,67-68) -----------------------
@@ -3346,10 +3525,35 @@ int scs_set_test_sparse(scs_ctx* c, int64_t N, int64_t nnz, const int64_t* rowpt
       upload_vals(c, c->val, val, nnz, c->sp_f32);
     }
     if (N > 0) h2d(c, c->y, y, N);
-    build_blocked(c, N, c->m, c->rowptr, c->colidx, c->val, c->bcsr);
-    alloc_nspace(c);
-    sync(c);
-    c->tset.on = true;
+    finish_sparse_test(c, N);
+  });
+}
+
+int scs_set_test_sparse_device(scs_ctx* c, int64_t N, int64_t nnz, const void* d_rowptr, int ptr_bytes,
+                               const void* d_colidx, int idx_bytes, const void* d_val, int val_bytes, int f32,
+                               const double* y, void* src_stream, int64_t Nglob, int64_t row0) {
+  if (!c) return SCS_ERR_ARG;
+  const SparseSrc s{d_rowptr, ptr_bytes, d_colidx, idx_bytes, d_val, val_bytes, (hipStream_t)src_stream,
+                    "scs_set_test_sparse_device"};
+  if (is_group(c)) return refuse_group_device(c, s.what);
+  return guarded(c, [&] {
+    HCK(hipSetDevice(c->dev));
+    if (!y) fail(c, SCS_ERR_ARG, "%s: y is NULL (the CSR arrays and y are both required)", s.what);
+    if (!c->has_data || c->generic)
+      fail(c, SCS_ERR_STATE, "test data needs a data problem: call scs_set_data / scs_gen_data / scs_set_sparse first");
+    check_sparse_src(c, s, N, c->m, nnz);
+    const CsrBufs b = ingest_csr(c, s, N, c->m, nnz, f32 ? 1 : 0);
+    free_test(c);
+    (void)row0;
+    test_view_dims(c, N, Nglob, true);
+    TestScope ts(c);
+    c->sp_f32 = f32 ? 1 : 0;
+    c->nnz = nnz;
+    c->rowptr = b.rowptr;
+    c->colidx = b.colidx;
+    c->val = b.val;
+    copy_y_any(c, y, N);
+    finish_sparse_test(c, N);
   });
 }
 

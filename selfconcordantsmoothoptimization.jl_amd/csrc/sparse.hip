@@ -420,6 +420,164 @@ hipError_t blk_scatter(const int64_t* ptr, const int* idx, const void* val, int 
   return hipGetLastError();
 }
 
+// ---- a CSR that is already on the device (scs_set_sparse_device) -----------------------------------
+// Ingest: one wave per row, four rows per workgroup (the shape of blk_count_kernel).  The source is
+// read once: pointers widened to int64, indices narrowed to int32 (compared against [0, m) in the
+// source width first), values cast to the stored type.  Validation is part of the same pass and no
+// load depends on an unchecked value: rowptr[r] and rowptr[r + 1] lie inside the N + 1 entries, and
+// a row's entries are read only after its bounds pass, for p in [max(p0, 0), min(p1, nnz)).  Every
+// fault of rowptr shows at some row (a start that is not 0 at row 0, an end that is not nnz at row
+// N - 1, anything between as a decrease), so "no flag" means a valid CSR.
+// rec[0] = min over faulty rows of 4·row + kind (CSR_START / CSR_ORDER / CSR_END), rec[1] = first
+// position with a column index outside [0, m); both start as all ones.
+enum { CSR_START = 0, CSR_ORDER = 1, CSR_END = 2 };
+
+template <typename PT, typename IT, typename SV, typename DV>
+__global__ void csr_ingest_kernel(const PT* __restrict__ rowptr, const IT* __restrict__ colidx,
+                                  const SV* __restrict__ val, int64_t N, int64_t m, int64_t nnz,
+                                  int64_t* __restrict__ optr, int* __restrict__ oidx, DV* __restrict__ oval,
+                                  unsigned long long* __restrict__ rec) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (N == 0) {   // the one entry of rowptr is both the start and the end
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      const int64_t p = (int64_t)rowptr[0];
+      optr[0] = p;
+      if (p != 0) atomicMin(rec, (unsigned long long)CSR_START);
+      else if (nnz != 0) atomicMin(rec, (unsigned long long)CSR_END);
+    }
+    return;
+  }
+  if (r >= N) return;
+  const int64_t p0 = (int64_t)rowptr[r], p1 = (int64_t)rowptr[r + 1];
+  if (lane == 0) {
+    optr[r] = p0;
+    if (r == N - 1) optr[N] = p1;
+  }
+  int kind = -1;
+  if (r == 0 && p0 != 0) kind = CSR_START;
+  else if (p1 < p0) kind = CSR_ORDER;
+  else if (r == N - 1 && p1 != nnz) kind = CSR_END;
+  if (kind >= 0) {
+    if (lane == 0) atomicMin(rec, (unsigned long long)r * 4 + (unsigned long long)kind);
+    return;
+  }
+  const int64_t a = p0 > 0 ? p0 : 0, b = p1 < nnz ? p1 : nnz;
+  for (int64_t p = a + lane; p < b; p += 64) {
+    const int64_t cw = (int64_t)colidx[p];   // widened, never narrowed, before the comparison
+    const bool ok = cw >= 0 && cw < m;
+    if (!ok) atomicMin(rec + 1, (unsigned long long)p);
+    oidx[p] = ok ? (int)cw : 0;
+    oval[p] = (DV)val[p];
+  }
+}
+
+template <typename PT, typename IT, typename SV>
+static void csr_ingest_v(const void* rowptr, const void* colidx, const void* val, int64_t N, int64_t m, int64_t nnz,
+                         int64_t* optr, int* oidx, void* oval, int f32, unsigned long long* rec, hipStream_t st) {
+  const dim3 grid((unsigned)ceil_div(std::max<int64_t>(N, 1), 4));
+  if (f32)
+    hipLaunchKernelGGL((csr_ingest_kernel<PT, IT, SV, float>), grid, dim3(256), 0, st, (const PT*)rowptr,
+                       (const IT*)colidx, (const SV*)val, N, m, nnz, optr, oidx, (float*)oval, rec);
+  else
+    hipLaunchKernelGGL((csr_ingest_kernel<PT, IT, SV, double>), grid, dim3(256), 0, st, (const PT*)rowptr,
+                       (const IT*)colidx, (const SV*)val, N, m, nnz, optr, oidx, (double*)oval, rec);
+}
+
+template <typename PT, typename IT>
+static void csr_ingest_i(const void* rowptr, const void* colidx, const void* val, int val_bytes, int64_t N, int64_t m,
+                         int64_t nnz, int64_t* optr, int* oidx, void* oval, int f32, unsigned long long* rec,
+                         hipStream_t st) {
+  if (val_bytes == 4) csr_ingest_v<PT, IT, float>(rowptr, colidx, val, N, m, nnz, optr, oidx, oval, f32, rec, st);
+  else csr_ingest_v<PT, IT, double>(rowptr, colidx, val, N, m, nnz, optr, oidx, oval, f32, rec, st);
+}
+
+template <typename PT>
+static void csr_ingest_p(const void* rowptr, const void* colidx, int idx_bytes, const void* val, int val_bytes,
+                         int64_t N, int64_t m, int64_t nnz, int64_t* optr, int* oidx, void* oval, int f32,
+                         unsigned long long* rec, hipStream_t st) {
+  if (idx_bytes == 4)
+    csr_ingest_i<PT, int32_t>(rowptr, colidx, val, val_bytes, N, m, nnz, optr, oidx, oval, f32, rec, st);
+  else
+    csr_ingest_i<PT, int64_t>(rowptr, colidx, val, val_bytes, N, m, nnz, optr, oidx, oval, f32, rec, st);
+}
+
+hipError_t csr_ingest(const void* rowptr, int ptr_bytes, const void* colidx, int idx_bytes, const void* val,
+                      int val_bytes, int64_t N, int64_t m, int64_t nnz, int64_t* optr, int* oidx, void* oval,
+                      int f32, unsigned long long* rec, hipStream_t st) {
+  if (ptr_bytes == 4)
+    csr_ingest_p<int32_t>(rowptr, colidx, idx_bytes, val, val_bytes, N, m, nnz, optr, oidx, oval, f32, rec, st);
+  else
+    csr_ingest_p<int64_t>(rowptr, colidx, idx_bytes, val, val_bytes, N, m, nnz, optr, oidx, oval, f32, rec, st);
+  return hipGetLastError();
+}
+
+// Transposition of a row-sorted CSR (after build_blocked's sort: equal column indices of a row are
+// adjacent, duplicates in their storage order).  Claim: the lane at the head of a run of equal
+// indices walks the run and takes `runlen` slots of its column with one integer atomicAdd; the
+// returned rank is kept at the head's position (32 bits: the door refuses nnz >= 2^32).  cnt then
+// goes through blk_scan to become colptr, and the place pass -- no atomics -- writes the run's
+// entries in order at colptr[c] + rank.  The ranks depend on arrival, the result does not: a run
+// stays together and in order, and the stable per-column sort by row that follows (build_blocked
+// on the CSC copy) orders the runs.
+__global__ void csr_claim_kernel(const int64_t* __restrict__ ptr, const int* __restrict__ idx, int64_t nrows,
+                                 unsigned long long* __restrict__ cnt, uint32_t* __restrict__ rank) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= nrows) return;
+  const int64_t p0 = ptr[r], p1 = ptr[r + 1];
+  for (int64_t p = p0 + lane; p < p1; p += 64) {
+    const int c = idx[p];
+    if (p == p0 || idx[p - 1] != c) {
+      int64_t q = p + 1;
+      while (q < p1 && idx[q] == c) ++q;
+      rank[p] = (uint32_t)atomicAdd(&cnt[c], (unsigned long long)(q - p));
+    }
+  }
+}
+
+template <typename VT>
+__global__ void csr_place_kernel(const int64_t* __restrict__ ptr, const int* __restrict__ idx,
+                                 const VT* __restrict__ val, int64_t nrows, const int64_t* __restrict__ colptr,
+                                 const uint32_t* __restrict__ rank, int* __restrict__ rowidx,
+                                 VT* __restrict__ valT) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= nrows) return;
+  const int64_t p0 = ptr[r], p1 = ptr[r + 1];
+  for (int64_t p = p0 + lane; p < p1; p += 64) {
+    const int c = idx[p];
+    if (p == p0 || idx[p - 1] != c) {
+      int64_t dst = colptr[c] + (int64_t)rank[p];
+      int64_t q = p;
+      do {
+        rowidx[dst] = (int)r;
+        valT[dst++] = val[q++];
+      } while (q < p1 && idx[q] == c);
+    }
+  }
+}
+
+hipError_t csr_claim(const int64_t* ptr, const int* idx, int64_t nrows, int64_t* cnt, uint32_t* rank, hipStream_t st) {
+  if (nrows <= 0) return hipSuccess;
+  hipLaunchKernelGGL(csr_claim_kernel, dim3((unsigned)ceil_div(nrows, 4)), dim3(256), 0, st, ptr, idx, nrows,
+                     (unsigned long long*)cnt, rank);
+  return hipGetLastError();
+}
+
+hipError_t csr_place(const int64_t* ptr, const int* idx, const void* val, int f32, int64_t nrows,
+                     const int64_t* colptr, const uint32_t* rank, int* rowidx, void* valT, hipStream_t st) {
+  if (nrows <= 0) return hipSuccess;
+  const dim3 grid((unsigned)ceil_div(nrows, 4));
+  if (f32)
+    hipLaunchKernelGGL(csr_place_kernel<float>, grid, dim3(256), 0, st, ptr, idx, (const float*)val, nrows, colptr,
+                       rank, rowidx, (float*)valT);
+  else
+    hipLaunchKernelGGL(csr_place_kernel<double>, grid, dim3(256), 0, st, ptr, idx, (const double*)val, nrows, colptr,
+                       rank, rowidx, (double*)valT);
+  return hipGetLastError();
+}
+
 // ---- sparse Gram G = Aᵀ diag(w) A priced by nnz (Σ_r nnz_r² multiply-adds, not N·m²) ------------
 // Jt*Q*Jt' of a SparseMatrixCSC (prox-GGN-SCORE.jl:114,129) and hess_fx = c·Aᵀ diag(h) A
 // (prox-N-SCORE.jl:55) on a sparse A.  Gustavson by output column: G(i, j) = Σ_{r ∈ rows(j)}

@@ -258,6 +258,63 @@ function DeviceProblem(A::SparseMatrixCSC{Float64}, y::AbstractVector, x0::Vecto
     return set_test!(model, Atest, ytest; Ntest_global, test_row0, val_f32)
 end
 
+# A sparse A that is already on the GPU (scs_set_sparse_device): the CSR triple of a
+# CuSparseMatrixCSR-style matrix as three device pointers -- rowptr (N + 1 entries of ptr_type), colidx
+# (nnz entries of idx_type, 0-BASED: subtract 1 on the device from a Julia-side 1-based array) and val
+# (nnz entries of elem) -- with their element types (Int32 / Int64, Float32 / Float64).  The library
+# validates the arrays, builds the CSC copy and both blocked copies on the device: no host copy.
+# val_f32 alone decides the stored type.  Unsorted rows and duplicate entries are kept as they are.
+# y, stream: as for the dense device method above.  Single-device contexts only.
+# Written against the header; never executed (no Julia / AMDGPU.jl on the build machines).
+csr_width(T::Type) = (T === Int32 || T === Int64) ? Cint(sizeof(T)) :
+                     throw(ArgumentError("pointer / index type is Int32 or Int64"))
+val_width(T::Type) = (T === Float32 || T === Float64) ? Cint(sizeof(T)) :
+                     throw(ArgumentError("elem is Float64 or Float32"))
+
+function DeviceProblem(rowptr::Ptr{Cvoid}, colidx::Ptr{Cvoid}, val::Ptr{Cvoid}, N::Integer, m::Integer,
+                       nnz::Integer, y::Union{AbstractVector,Ptr{Cvoid}}, x0::Vector{Float64}, loss::Symbol, λ;
+                       ptr_type::Type=Int64, idx_type::Type=Int32, elem::Type=Float64, val_f32::Bool=false,
+                       stream::Ptr{Cvoid}=C_NULL,
+                       out_fn::Union{Symbol,Nothing}=nothing, scale::Float64=1.0 / N,
+                       L=nothing, sol::Vector{Float64}=zero(x0), C_set=nothing, P=nothing, device::Integer=0,
+                       N_global::Integer=N, row0::Integer=0)
+    length(x0) == m || throw(DimensionMismatch("x0 has $(length(x0)) entries, A has $m columns"))
+    pb, ib, vb = csr_width(ptr_type), csr_width(idx_type), val_width(elem)
+    ctx = create_ctx(device, nothing, :rccl)
+    yroot, yp = device_y(y, N)
+    GC.@preserve yroot chk(ccall((:scs_set_sparse_device, lib), Cint,
+              (Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint, Cint,
+               Ptr{Float64}, Ptr{Cvoid}, Int64, Int64),
+              ctx, N, m, nnz, rowptr, pb, colidx, ib, val, vb, val_f32 ? 1 : 0, yp, stream, N_global, row0), ctx)
+    return finish_problem(ctx, nothing, y isa Ptr ? nothing : yroot, x0, loss, λ, out_fn, scale, L, sol, C_set, P)
+end
+
+# CSR held-out rows from device memory (scs_set_test_sparse_device), as the method above takes A
+function set_test_sparse_device!(model::DeviceProblem, rowptr::Ptr{Cvoid}, colidx::Ptr{Cvoid}, val::Ptr{Cvoid},
+                                 Ntest::Integer, nnz::Integer, ytest::Union{AbstractVector,Ptr{Cvoid}};
+                                 ptr_type::Type=Int64, idx_type::Type=Int32, elem::Type=Float64,
+                                 val_f32::Bool=false, stream::Ptr{Cvoid}=C_NULL, Ntest_global::Integer=0,
+                                 test_row0::Integer=0)
+    pb, ib, vb = csr_width(ptr_type), csr_width(idx_type), val_width(elem)
+    yroot, yp = device_y(ytest, Ntest)
+    GC.@preserve yroot chk(ccall((:scs_set_test_sparse_device, lib), Cint,
+              (Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint, Cint,
+               Ptr{Float64}, Ptr{Cvoid}, Int64, Int64),
+              model.ctx, Ntest, nnz, rowptr, pb, colidx, ib, val, vb, val_f32 ? 1 : 0, yp, stream, Ntest_global,
+              test_row0), model.ctx)
+    return model
+end
+
+# the device's CSC copy of a sparse A, back on the host as a SparseMatrixCSC (values widened)
+function get_sparse_csc(model::DeviceProblem, N::Integer, m::Integer)
+    n = Ref{Int64}(0)
+    chk(ccall((:scs_get_nnz, lib), Cint, (Ptr{Cvoid}, Ref{Int64}), model.ctx, n), model.ctx)
+    colptr = zeros(Int64, m + 1); rowidx = zeros(Int32, max(n[], 1)); valT = zeros(Float64, max(n[], 1))
+    chk(ccall((:scs_get_sparse_csc, lib), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int32}, Ptr{Float64}),
+              model.ctx, colptr, rowidx, valT), model.ctx)
+    return SparseMatrixCSC(N, m, colptr .+ 1, Int64.(rowidx[1:n[]]) .+ 1, valT[1:n[]])
+end
+
 # ---- user losses outside the menu: the reference's own keyword callbacks ------------------
 # Problem(x0, f, λ; grad_fx, hess_fx) (problems.jl:44-59) / Problem(A, y, x0, f, λ; grad_fx,
 # hess_fx) (:61-81) evaluated on the host (SCS_LOSS_CALLBACK); the smoother, the solve, damping,

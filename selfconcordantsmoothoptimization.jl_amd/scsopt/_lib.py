@@ -132,6 +132,13 @@ _SIGS = {
     "scs_gen_sparse": (C.c_int, [C.c_void_p, C.POINTER(Synth), C.c_int]),
     "scs_get_nnz": (C.c_int, [C.c_void_p, c_i64p]),
     "scs_get_sparse": (C.c_int, [C.c_void_p, c_i64p, c_i32p, c_dp]),
+    "scs_get_sparse_csc": (C.c_int, [C.c_void_p, c_i64p, c_i32p, c_dp]),
+    "scs_set_sparse_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p,
+                                        C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
+                                        C.c_int64]),
+    "scs_set_test_sparse_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int, C.c_void_p,
+                                             C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
+                                             C.c_int64]),
     "scs_set_loss": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double]),
     "scs_set_loss_callback": (C.c_int, [C.c_void_p, LOSS_FN, C.c_void_p, C.c_int64]),
     "scs_set_reg": (C.c_int, [C.c_void_p, C.c_int, c_dp, C.c_int, c_dp, c_dp, C.c_int64, c_i64p, C.c_int64]),
@@ -269,6 +276,88 @@ def parse_device_vector(iface, n):
     if strides is not None and n > 1 and int(strides[0]) != 8:
         raise ValueError("a device y must be contiguous")
     return int(iface["data"][0] or 0)
+
+
+def _is_torch_tensor(a):
+    return type(a).__module__.split(".")[0] == "torch" and hasattr(a, "layout")
+
+
+def is_device_csr(A):
+    """A CSR matrix whose three arrays live on the GPU: a 2-D torch tensor with layout ==
+    torch.sparse_csr on a GPU, or any object with indptr / indices / data / shape whose arrays expose
+    __cuda_array_interface__ (CuPy's csr_matrix).  A torch sparse tensor this door cannot take raises
+    ValueError with what to call instead: a COO (or CSC / blocked) layout, a batched CSR, a CPU tensor."""
+    if A is None or isinstance(A, np.ndarray):
+        return False
+    if _is_torch_tensor(A):
+        torch = sys.modules["torch"]
+        if A.layout == torch.strided:
+            return False
+        if A.layout != torch.sparse_csr:
+            raise ValueError(f"a torch sparse tensor with layout {A.layout}: the device door takes CSR -- call "
+                             "A.to_sparse_csr() first")
+        if A.dim() != 2:
+            raise ValueError(f"a batched CSR tensor of shape {tuple(A.shape)}: pass one 2-D matrix (A[i]) per "
+                             "problem")
+        if not A.is_cuda:
+            raise ValueError("a CPU sparse torch tensor: move it to the GPU (A.to('cuda')) for the device door, "
+                             "or pass a scipy.sparse matrix for the host door")
+        return True
+    try:
+        parts = (A.indptr, A.indices, A.data)
+        A.shape
+    except AttributeError:
+        return False
+    return all(is_device_array(p) for p in parts)
+
+
+def device_csr_arrays(A):
+    """(shape, indptr, indices, data) of a matrix that passed is_device_csr; nothing is copied."""
+    if _is_torch_tensor(A):
+        return tuple(A.shape), A.crow_indices(), A.col_indices(), A.values()
+    return tuple(A.shape), A.indptr, A.indices, A.data
+
+
+def _parse_csr_array(iface, name, types, n):
+    typestr = iface["typestr"]
+    if typestr not in types:
+        raise TypeError(f"device CSR {name} of type {typestr!r}: one of {sorted(types)} is needed")
+    es = types[typestr]
+    shape = tuple(int(v) for v in iface["shape"])
+    if shape != (n,):
+        raise ValueError(f"device CSR {name} has shape {shape}, expected ({n},)")
+    strides = iface.get("strides")
+    if strides is not None and n > 1 and int(strides[0]) != es:
+        raise ValueError(f"device CSR {name} must be contiguous (stride {int(strides[0])} bytes for {es}-byte "
+                         "elements); it is not copied here")
+    ptr = iface["data"][0]
+    stream = iface.get("stream")
+    if stream is not None and int(stream) == 0:
+        raise ValueError("__cuda_array_interface__ forbids stream = 0 (1 and 2 name the default streams)")
+    return (int(ptr) if ptr else 0), es, (None if stream is None else int(stream))
+
+
+def parse_device_csr(shape, iface_ptr, iface_idx, iface_val):
+    """The matrix shape and the __cuda_array_interface__ dicts of indptr / indices / data -> what
+    scs_set_sparse_device takes: {"rowptr", "ptr_bytes", "colidx", "idx_bytes", "val", "val_bytes", "N",
+    "m", "nnz", "stream"}.  "<i4" / "<i8" index arrays and "<f4" / "<f8" values (anything else:
+    TypeError), each contiguous, of lengths N + 1, nnz and nnz (ValueError otherwise); nothing is copied.
+    With nnz = 0 the data pointers may be null.  `stream` is the first stream entry the three
+    interfaces name (None, 1, 2 or a handle, as parse_device_matrix returns it)."""
+    shape = tuple(int(v) for v in shape)
+    if len(shape) != 2:
+        raise ValueError(f"a device CSR matrix has two dimensions, this one has shape {shape}")
+    N, m = shape
+    nnz = int(tuple(iface_val["shape"])[0]) if len(tuple(iface_val["shape"])) == 1 else -1
+    ints, floats = {"<i4": 4, "<i8": 8}, {"<f4": 4, "<f8": 8}
+    rp, pb, s0 = _parse_csr_array(iface_ptr, "indptr", ints, N + 1)
+    if nnz < 0:
+        raise ValueError(f"device CSR data has shape {tuple(iface_val['shape'])}, expected one dimension")
+    ci, ib, s1 = _parse_csr_array(iface_idx, "indices", ints, nnz)
+    va, vb, s2 = _parse_csr_array(iface_val, "data", floats, nnz)
+    stream = next((s for s in (s0, s1, s2) if s is not None), None)
+    return {"rowptr": rp, "ptr_bytes": pb, "colidx": ci, "idx_bytes": ib, "val": va, "val_bytes": vb, "N": N, "m": m,
+            "nnz": nnz, "stream": stream}
 
 
 class Context:

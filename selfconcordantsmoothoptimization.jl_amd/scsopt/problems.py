@@ -115,9 +115,12 @@ class Problem:
             # y keeps its shape: an N x ny target is a multi-output problem (iterate.jl:105-107)
             self._cb_data = None if A is None else (A, np.asarray(y, dtype=np.float64))
             A, y, self.generic = None, None, True
-        if devices is not None and (comm is not None or _is_sparse(A)):
+        # a device CSR is asked for before _is_sparse: a CuPy csr_matrix has tocsr / tocsc / nnz as well
+        dev_csr = _lib.is_device_csr(A)
+        if devices is not None and (comm is not None or (_is_sparse(A) and not dev_csr)):
             raise ValueError("devices=[...] (one process, several GPUs) takes a dense A and no comm")
-        if devices is not None and (_lib.is_device_array(A) or _lib.is_device_array(Atest)):
+        if devices is not None and (_lib.is_device_array(A) or _lib.is_device_array(Atest) or dev_csr
+                                    or _lib.is_device_csr(Atest)):
             raise ValueError("devices=[...] splits host rows across its GPUs: a device array lives on one of them "
                              "(pass a host array, or one process per GPU with a row slice each)")
         self.ctx = _ctx if _ctx is not None else _lib.Context(device, devices=devices, device_exchange=device_exchange)
@@ -130,6 +133,8 @@ class Problem:
             if self.generic:
                 self.N = 0
                 self.ctx.check(_lib.lib.scs_set_data(self.ctx.h, 0, self.m, None, 0, None, 0, 0))
+            elif dev_csr:
+                self.N = self._set_sparse_device(A, y, False, N_global, row0, bool(sparse_f32))
             elif _is_sparse(A):
                 self._set_sparse(A, y, N_global, row0, f32=bool(sparse_f32))
             elif _lib.is_device_array(A):
@@ -211,6 +216,12 @@ class Problem:
             self.ctx.check(_lib.lib.scs_set_test_callback(self.ctx.h, 1))
             self.test_model = True
             return
+        if _lib.is_device_csr(Atest):
+            if len(self.ctx.devices) > 1:
+                raise ValueError("a devices=[...] problem takes host held-out rows, not a device CSR")
+            self._set_sparse_device(Atest, ytest, True, Ntest_global, row0, bool(sparse_f32))
+            self.test_model = True
+            return
         if _lib.is_device_array(Atest):
             if len(self.ctx.devices) > 1:
                 raise ValueError("a devices=[...] problem takes host held-out rows, not a device array")
@@ -251,34 +262,11 @@ class Problem:
         copy.  Row- or column-major, float64 or float32; the stored type follows dense_f32 as for host
         arrays (float32 kept only with dense_f32=True, float64 rounded on the device with it).
         Returns N."""
-        torch_stream = None
-        for a in (A, y):
-            if type(a).__module__.split(".")[0] == "torch":
-                _lib.require_torch_runtime("a torch tensor as A / y")   # a second runtime's pointer is not ours
-                torch_stream = sys.modules["torch"].cuda.current_stream(a.device)
         d = _lib.parse_device_matrix(A.__cuda_array_interface__)
         if d["m"] != self.m:
             raise ValueError(f"A must be N x m with m = length(x0) = {self.m}")
         N = d["N"]
-        if _lib.is_device_array(y):
-            yi = y.__cuda_array_interface__
-            yp, yv = _lib.parse_device_vector(yi, N), None
-            ystream = yi.get("stream")
-        else:
-            yv = np.ascontiguousarray(np.asarray(y, dtype=np.float64).reshape(-1))
-            if yv.shape[0] != N:
-                raise ValueError(f"y has {yv.shape[0]} entries, A has {N} rows")
-            yp, ystream = yv.ctypes.data, None
-        stream = d["stream"]
-        if stream is None and ystream is not None:
-            stream = int(ystream)
-        if stream is None and torch_stream is not None:
-            # torch's interface names no stream: the tensor's producer is the current one (its default
-            # stream is drained here: a handle of 0 would read as "the source is complete")
-            if torch_stream.cuda_stream:
-                stream = int(torch_stream.cuda_stream)
-            else:
-                torch_stream.synchronize()
+        yp, stream, _keep = self._device_y_and_stream((A,), y, N, d["stream"])
         if self.dense_f32:
             self.ctx.check(_lib.lib.scs_set_dense_f32(self.ctx.h, 1))
         Ng = 0 if N_global is None else int(N_global)
@@ -288,6 +276,57 @@ class Problem:
         else:
             rc = _lib.lib.scs_set_data_device(self.ctx.h, N, self.m, d["ptr"], d["elem_bytes"], d["stride_n"],
                                               d["stride_m"], yp, stream, Ng if Ng else N, int(row0))
+        self.ctx.check(rc)
+        return N
+
+    def _device_y_and_stream(self, arrays, y, N, stream):
+        """y of a device door (a device array or anything NumPy reads) and the src_stream to pass:
+        `stream` if the source's interface named one, else y's, else torch's current stream.  Returns
+        (pointer of y, stream, the host copy of y to keep alive or None)."""
+        torch_stream = None
+        for a in (*arrays, y):
+            if type(a).__module__.split(".")[0] == "torch":
+                _lib.require_torch_runtime("a torch tensor as A / y")   # a second runtime's pointer is not ours
+                torch_stream = sys.modules["torch"].cuda.current_stream(a.device)
+        if _lib.is_device_array(y):
+            yi = y.__cuda_array_interface__
+            yp, yv = _lib.parse_device_vector(yi, N), None
+            ystream = yi.get("stream")
+        else:
+            yv = np.ascontiguousarray(np.asarray(y, dtype=np.float64).reshape(-1))
+            if yv.shape[0] != N:
+                raise ValueError(f"y has {yv.shape[0]} entries, A has {N} rows")
+            yp, ystream = yv.ctypes.data, None
+        if stream is None and ystream is not None:
+            stream = int(ystream)
+        if stream is None and torch_stream is not None:
+            # torch's interface names no stream: the tensor's producer is the current one (its default
+            # stream is drained here: a handle of 0 would read as "the source is complete")
+            if torch_stream.cuda_stream:
+                stream = int(torch_stream.cuda_stream)
+            else:
+                torch_stream.synchronize()
+        return yp, stream, yv
+
+    def _set_sparse_device(self, A, y, test, N_global, row0, f32):
+        """A CSR matrix whose arrays are already on the GPU (torch.sparse_csr_tensor, a CuPy csr_matrix):
+        scs_set_sparse_device / scs_set_test_sparse_device validate it, build the CSC copy and both
+        blocked copies on the device, no host copy.  int32 or int64 pointers and indices, float32 or
+        float64 values; f32 (sparse_f32) alone decides the stored type.  Unsorted rows and duplicate
+        entries are taken as scipy's tocsr() / tocsc() keep them.  Returns N."""
+        shape, indptr, indices, data = _lib.device_csr_arrays(A)
+        d = _lib.parse_device_csr(shape, *(a.__cuda_array_interface__ for a in (indptr, indices, data)))
+        if d["m"] != self.m:
+            raise ValueError(f"A must be N x m with m = length(x0) = {self.m}")
+        N = d["N"]
+        yp, stream, _keep = self._device_y_and_stream((indptr, indices, data), y, N, d["stream"])
+        Ng = 0 if N_global is None else int(N_global)
+        src = (d["rowptr"], d["ptr_bytes"], d["colidx"], d["idx_bytes"], d["val"], d["val_bytes"], 1 if f32 else 0,
+               yp, stream)
+        if test:
+            rc = _lib.lib.scs_set_test_sparse_device(self.ctx.h, N, d["nnz"], *src, Ng, int(row0))
+        else:
+            rc = _lib.lib.scs_set_sparse_device(self.ctx.h, N, self.m, d["nnz"], *src, Ng if Ng else N, int(row0))
         self.ctx.check(rc)
         return N
 
@@ -464,6 +503,18 @@ class Problem:
         y = np.zeros(self.N, dtype=np.float64)
         self.ctx.check(_lib.lib.scs_get_data(self.ctx.h, 0, self.N, None, self.N, dptr(y)))
         return sp.csr_matrix((val[:nnz], colidx[:nnz], rowptr), shape=(self.N, self.m)), y
+
+    def get_sparse_csc(self):
+        """The device CSC copy of A as a scipy.sparse.csc_matrix (values widened to fp64), entries as
+        the device holds them: rows ascending within a column, duplicates kept."""
+        import scipy.sparse as sp
+        nnz = self.nnz
+        colptr = np.zeros(self.m + 1, dtype=np.int64)
+        rowidx = np.zeros(max(nnz, 1), dtype=np.int32)
+        valT = np.zeros(max(nnz, 1), dtype=np.float64)
+        self.ctx.check(_lib.lib.scs_get_sparse_csc(self.ctx.h, colptr.ctypes.data_as(_lib.c_i64p),
+                                                   rowidx.ctypes.data_as(_lib.c_i32p), dptr(valT)))
+        return sp.csc_matrix((valT[:nnz], rowidx[:nnz], colptr), shape=(self.N, self.m))
 
     # device evaluation helpers ------------------------------------------------
     def fx(self, x):
