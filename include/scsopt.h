@@ -47,14 +47,18 @@ enum scs_loss_kind {
   SCS_LOSS_LEAST_SQUARES = 3,   /* 0.5*sum((A*x-y).^2)*c           README.md:212-214 */
   SCS_LOSS_QUADRATIC = 4,       /* 1/2*(x'*(A*x)) + y'*x             test/test_algs.jl:90 */
   SCS_LOSS_ROSENBROCK = 5,      /* chained Rosenbrock, no data        README.md:49 */
-  SCS_LOSS_CALLBACK = 6         /* the caller's f / grad_fx / hess_fx (scs_set_loss_callback) */
+  SCS_LOSS_CALLBACK = 6,        /* the caller's f / grad_fx / hess_fx (scs_set_loss_callback) */
+  SCS_LOSS_SAMPLEWISE = 7       /* f = sum_i l(y_i, a_i'x): the caller's l, dl/dz, d2l/dz2 on z = A*x
+                                   (scs_set_loss_samplewise); the device keeps A and every product */
 };
 
 /* (out_fn, f(y, ŷ)) pairs used by ProxGGNSCORE (prox-GGN-SCORE.jl:44-56).    */
 enum scs_ggn_kind {
   SCS_GGN_NONE = 0,
   SCS_GGN_SIGMOID_CE = 1,       /* Mfunc = sigmoid(A*x), CE on ŷ   test/test_algs.jl:10-11 */
-  SCS_GGN_LINEAR_LS = 2         /* out_fn = A*x, 0.5*c*sum((ŷ-y).^2) README.md:233-239 */
+  SCS_GGN_LINEAR_LS = 2,        /* out_fn = A*x, 0.5*c*sum((ŷ-y).^2) README.md:233-239 */
+  SCS_GGN_SAMPLEWISE = 3        /* ŷ_i = φ(a_i'x), f = sum_i l(y_i, ŷ_i): the caller's dŷ/dz, df/dŷ, d2f/dŷ2
+                                   (scs_set_loss_samplewise with has_ggn) */
 };
 
 /* reg_name strings of get_reg / invoke_prox (regularizers.jl:4-31,
@@ -206,6 +210,36 @@ int scs_set_reduce_buffer(scs_ctx* ctx, void* dev_ptr, int64_t ndoubles);
 #define SCS_CB_NO_METHOD 2
 typedef int (*scs_loss_fn)(void* user, int what, const double* x, int64_t m, double* out);
 int scs_set_loss_callback(scs_ctx* ctx, scs_loss_fn fn, void* user, int64_t ggn_rows);
+
+/* ---- sample-wise losses outside the menu: f(A, y, x) = sum_i l(y_i, z_i), z = A*x ---------
+ * SCS_LOSS_SAMPLEWISE keeps the data and every product with A on the device (dense fp64 / fp32,
+ * sparse, both device doors, row shards, minibatches, the held-out set); the caller supplies N
+ * numbers per derivative from z and y.  `what` is a bit set:
+ *   SCS_SW_VALUE  val[i] = l(y_i, z_i), already scaled (the library applies no scale)
+ *   SCS_SW_D1     d1[i]  = dl/dz_i
+ *   SCS_SW_D2     d2[i]  = d2l/dz_i2
+ *   SCS_SW_GGN    s[i] = dŷ_i/dz_i, d1[i] = r_i = df/dŷ_i, d2[i] = q_i = d2f/dŷ_i2 (a diagonal
+ *                 hess_fy; prox-GGN-SCORE.jl:44-49 with ŷ_i = φ(z_i)); never together with D1 / D2
+ * n: the rows of the view in use (this rank's data rows, a minibatch view, the held-out view --
+ * ftest is the same callback on that view's z, y); z, y and every output have n entries; outputs
+ * not asked for must not be written.  device_ptrs = 0: host arrays owned by the library (z and
+ * the requested outputs cross per call, y once per view), `stream` is NULL.  device_ptrs = 1: the
+ * library's device buffers and the context's stream: the callback queues its work on that stream
+ * (or completes it before it returns); the library does not synchronise around the call.  Return
+ * 0; anything else fails the calling function with SCS_ERR_CALLBACK.
+ * scs_set_loss(ctx, SCS_LOSS_SAMPLEWISE, SCS_GGN_NONE | SCS_GGN_SAMPLEWISE, 1.0) selects it
+ * (scale != 1 and SCS_GGN_SAMPLEWISE without has_ggn: SCS_ERR_ARG).  A multi-device group
+ * context is refused (SCS_ERR_ARG): its devices run one host thread each.  There is no automatic
+ * differentiation: ProxNSCORE asks D2, ProxGGNSCORE GGN.  scs_iterate's fused ProxLQNSCORE epoch
+ * (m >= 16384) is not taken by this kind: the unfused device-resident epoch runs instead.
+ * (scs_samplewise_fn is declared as a function type and passed by pointer.)                  */
+#define SCS_SW_VALUE 1
+#define SCS_SW_D1 2
+#define SCS_SW_D2 4
+#define SCS_SW_GGN 8
+typedef int (scs_samplewise_fn)(void* user, int what, int64_t n, const double* z, const double* y, double* val,
+                                double* d1, double* d2, double* s, void* stream);
+int scs_set_loss_samplewise(scs_ctx* ctx, scs_samplewise_fn* fn, void* user, int device_ptrs, int has_ggn);
 
 /* ---- data  (Problem(A, y, ...) -- problems.jl:61-81) --------------------- */
 /* Upload host A (column-major, N x m, leading dim lda) and y (N).  N is the

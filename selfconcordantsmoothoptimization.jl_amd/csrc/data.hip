@@ -186,6 +186,60 @@ hipError_t launch_epilogue(int loss, int ggn, int flags, const double* zpart, in
   return hipGetLastError();
 }
 
+// SCS_LOSS_SAMPLEWISE: the same outputs from the caller's per-sample numbers (val = l, d1 = dl/dz | r,
+// d2 = d²l/dz² | q, s = dŷ/dz) instead of a closed form; epilogue_kernel's block structure (256 samples
+// per block, block_sum<256>, one partial per block) and, for the GGN products, its operation order.
+// Rows N <= n < Npad are written as zeros whatever the caller's buffers hold there (A's padding rows
+// are zero, and 0·NaN would poison Aᵀv and the Gram); the buffers are read for n < N only.
+__global__ __launch_bounds__(256) void samplewise_epilogue_kernel(int flags, const double* __restrict__ val,
+                                                                  const double* __restrict__ d1,
+                                                                  const double* __restrict__ d2,
+                                                                  const double* __restrict__ sv, int64_t N,
+                                                                  int64_t Npad, double* __restrict__ gout,
+                                                                  double* __restrict__ hout,
+                                                                  double* __restrict__ wout,
+                                                                  double* __restrict__ vout,
+                                                                  double* __restrict__ valpart) {
+  __shared__ double sh[4];
+  double acc = 0.0;
+  const int64_t n = (int64_t)blockIdx.x * EPI_PER_BLOCK + threadIdx.x;
+  if (n < Npad) {
+    if (n >= N) {
+      if (flags & EPI_GRAD) gout[n] = 0.0;
+      if (flags & EPI_HESS) hout[n] = 0.0;
+      if (flags & EPI_GGN) { wout[n] = 0.0; vout[n] = 0.0; }
+      if (flags & EPI_SQR) { gout[n] = 0.0; hout[n] = 0.0; }
+    } else {
+      if (flags & EPI_VAL) acc += val[n];
+      if (flags & EPI_GRAD) gout[n] = d1[n];
+      if (flags & EPI_HESS) hout[n] = d2[n];
+      if (flags & EPI_GGN) {
+        const double s = sv[n], r = d1[n], q = d2[n];
+        if (flags & EPI_SQR) {   // sample-space branch: the factors themselves
+          gout[n] = s;
+          hout[n] = q;
+          wout[n] = r;
+        } else {
+          wout[n] = s * s * q;
+          vout[n] = s * r;
+        }
+      }
+    }
+  }
+  if (flags & EPI_VAL) {
+    const double s = block_sum<256>(acc, sh);
+    if (threadIdx.x == 0) valpart[blockIdx.x] = s;
+  }
+}
+
+hipError_t launch_samplewise_epilogue(int flags, const double* val, const double* d1, const double* d2,
+                                      const double* s, int64_t N, int64_t Npad, double* g, double* h, double* w,
+                                      double* v, double* valpart, hipStream_t st) {
+  hipLaunchKernelGGL(samplewise_epilogue_kernel, dim3(epilogue_blocks(Npad)), dim3(256), 0, st, flags, val, d1, d2, s,
+                     N, Npad, g, h, w, v, valpart);
+  return hipGetLastError();
+}
+
 __global__ __launch_bounds__(1024) void sum_partials_kernel(const double* __restrict__ part, int n,
                                                             double* __restrict__ out) {
   __shared__ double sh[16];

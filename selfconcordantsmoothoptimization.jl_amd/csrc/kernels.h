@@ -357,6 +357,12 @@ int epilogue_blocks(int64_t Npad);
 hipError_t launch_epilogue(int loss, int ggn, int flags, const double* zpart, int nsplit, int64_t ldz,
                            const double* y, int64_t N, int64_t Npad, double c, double* z, double* g, double* h,
                            double* w, double* v, double* valpart, hipStream_t st);
+// SCS_LOSS_SAMPLEWISE: what launch_epilogue writes for `flags` (EPI_Z excluded: z is materialised
+// before the caller's functions see it), from the caller's per-sample val / d1 / d2 / s (n < N read;
+// rows N..Npad written as zeros); the same epilogue_blocks(Npad) value partials
+hipError_t launch_samplewise_epilogue(int flags, const double* val, const double* d1, const double* d2,
+                                      const double* s, int64_t N, int64_t Npad, double* g, double* h, double* w,
+                                      double* v, double* valpart, hipStream_t st);
 // out[0] = Σ part[0..n)  (fixed order)
 hipError_t launch_sum_partials(const double* part, int n, double* out, hipStream_t st);
 hipError_t launch_marker(hipStream_t st);

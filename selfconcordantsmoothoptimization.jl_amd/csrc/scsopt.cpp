@@ -191,6 +191,27 @@ struct scs_ctx {
   int64_t cb_nout = 0;        // rows of the SCS_CB_GGN Jacobian (0: no GGN callback)
   NView cbv;                  // that Jacobian, panel-blocked, swapped in for the GGN step
   double* cbstage = nullptr;  // column-major staging panel for its upload
+  // SCS_LOSS_SAMPLEWISE (scs_set_loss_samplewise): the caller's per-sample functions of z = A x and y.
+  // swd: device [z scratch | val | d1 | d2 | s], sw_cap doubles each (the largest view seen); swh: the
+  // same five areas in pinned host memory (host mode); swy: pinned copies of the views' y (host mode),
+  // keyed by the device pointer, the row count and y_stamp, which moves whenever a view's y is
+  // (re)written or its buffer could be reused -- y crosses once per view, not once per call
+  scs_samplewise_fn* sw = nullptr;
+  void* sw_user = nullptr;
+  bool sw_dev = false, sw_ggn = false;
+  double* swd = nullptr;
+  int64_t sw_cap = 0;
+  double* swh = nullptr;
+  int64_t swh_cap = 0;
+  struct SwY {
+    const double* key = nullptr;
+    int64_t n = -1;
+    uint64_t stamp = 0;
+    double* h = nullptr;
+    int64_t cap = 0;
+  } swy[4];
+  int swy_next = 0;
+  uint64_t y_stamp = 1;
   const double* gfix = nullptr; // scs_step_grad: the caller's ∇fx (device copy) for the step's duration
   bool lbfgs_pending = false; // scs_iterate's device loop: the memory update's dg/gg are read at the epoch end
   int lbfgs_slot = 0;
@@ -680,6 +701,7 @@ void alloc_mspace(scs_ctx* c) {
 
 void alloc_nspace(scs_ctx* c) {
   if (c->generic) return;
+  ++c->y_stamp;   // a new view: its y is (re)written by the caller of this function
   c->nsplit = c->sparse ? c->bcsr.nblk : gemv_n_splits(c->Npad, c->m);
   c->nval = epilogue_blocks(c->Npad);
   c->nchunk = c->sparse ? c->bcsc.nblk : gemv_t_chunks(c->Npad);
@@ -931,6 +953,7 @@ void swap_view(scs_ctx* c, NView& v) {
 }
 
 void free_view(scs_ctx* c, NView& v) {
+  ++c->y_stamp;   // a later allocation may reuse y's address
   for (double** p : {&v.A, &v.y, &v.zpart, &v.z, &v.gN, &v.hN, &v.wN, &v.vN, &v.valpart, &v.tpart, &v.At, &v.Ps,
                      &v.Ms, &v.bS, &v.uN, &v.hvec, &v.hg})
     dfree_t(c, *p);
@@ -1051,6 +1074,7 @@ void select_batch(scs_ctx* c, int64_t b) {
   }
   if (c->bheld[k] != b) {
     NView& v = c->bpool[k];
+    ++c->y_stamp;   // the view's y is gathered again
     if (n == 0) {
       HCK(hipMemsetAsync(v.A, 0, a_block_bytes(c, v.Npad, v.a32), c->st));
       HCK(hipMemsetAsync(v.y, 0, sizeof(double) * v.Npad, c->st));
@@ -1121,6 +1145,104 @@ void require_dense(scs_ctx* c, const char* what) {
   if (c->a32) fail(c, SCS_ERR_ARG, "%s needs an fp64-stored A: fp32 storage (scs_set_dense_f32) does not cover it", what);
 }
 
+// SCS_LOSS_SAMPLEWISE, host mode: the pinned copy of the current view's y (n entries), downloaded when
+// the view (device pointer, rows, y_stamp) is not among the four held
+const double* sw_host_y(scs_ctx* c) {
+  const int64_t n = c->N;
+  for (auto& e : c->swy)
+    if (e.key == c->y && e.n == n && e.stamp == c->y_stamp) return e.h;
+  auto& e = c->swy[c->swy_next];
+  c->swy_next = (c->swy_next + 1) % 4;
+  e.key = nullptr;
+  if (e.cap < n) {
+    if (e.h) HCK(hipHostFree(e.h));
+    e.h = nullptr;
+    e.cap = 0;
+    HCK(hipHostMalloc((void**)&e.h, std::max<int64_t>(n, 1) * sizeof(double), hipHostMallocDefault));
+    e.cap = std::max<int64_t>(n, 1);
+  }
+  if (n > 0) d2h(c, e.h, c->y, n);
+  sync(c);
+  e.key = c->y;
+  e.n = n;
+  e.stamp = c->y_stamp;
+  return e.h;
+}
+
+// The loss epilogue of the current view: every launch_epilogue of the data path goes through here.
+// zpart: `ns` z-partials (stride Npad); zout: where z goes with EPI_Z.  The menu kinds launch
+// epilogue_kernel.  SCS_LOSS_SAMPLEWISE (1) materialises z (the EPI_Z pass of epilogue_kernel: into
+// zout with EPI_Z, else into scratch -- a line-search trial or the held-out set must not overwrite the
+// cached c->z; one partial without EPI_Z is z already), (2) asks the caller's functions for exactly
+// what `flags` needs and (3) launches samplewise_epilogue_kernel over their output.
+void loss_epilogue(scs_ctx* c, int flags, const double* zpart, int ns, double* zout) {
+  if (c->loss != SCS_LOSS_SAMPLEWISE) {
+    HCK(launch_epilogue(c->loss, c->ggn, flags, zpart, ns, c->Npad, c->y, c->N, c->Npad, c->scale, zout, c->gN, c->hN,
+                        c->wN, c->vN, c->valpart, c->st));
+    return;
+  }
+  const int need = flags & ~EPI_Z;
+  if (!c->sw) fail(c, SCS_ERR_STATE, "no sample-wise loss functions: call scs_set_loss_samplewise");
+  const int64_t N = c->N, Npad = c->Npad;
+  if (need && c->sw_cap < Npad) {
+    dfree_t(c, c->swd);
+    c->sw_cap = 0;
+    c->swd = dalloc<double>(c, 5 * (size_t)Npad);
+    c->sw_cap = Npad;
+  }
+  const double* z = zpart;
+  if ((flags & EPI_Z) || ns != 1) {
+    double* zm = (flags & EPI_Z) ? zout : c->swd;
+    if (zm != zpart || ns != 1)
+      HCK(launch_epilogue(SCS_LOSS_LEAST_SQUARES, SCS_GGN_NONE, EPI_Z, zpart, ns, Npad, c->y, N, Npad, 1.0, zm, nullptr,
+                          nullptr, nullptr, nullptr, c->valpart, c->st));
+    z = zm;
+  }
+  if (!need) return;
+  int what = 0;
+  if (need & EPI_VAL) what |= SCS_SW_VALUE;
+  if (need & EPI_GRAD) what |= SCS_SW_D1;
+  if (need & EPI_HESS) what |= SCS_SW_D2;
+  if (need & EPI_GGN) {
+    if (need & (EPI_GRAD | EPI_HESS)) fail(c, SCS_ERR_ARG, "sample-wise loss: d1 / d2 carry r / q of the GGN request");
+    if (!c->sw_ggn) fail(c, SCS_ERR_ARG, "ProxGGNSCORE needs an out_fn / GGN loss kind (scs_set_loss_samplewise "
+                                         "without has_ggn)");
+    what |= SCS_SW_GGN;
+  }
+  double *dv = c->swd + c->sw_cap, *d1 = dv + c->sw_cap, *d2 = d1 + c->sw_cap, *ds = d2 + c->sw_cap;
+  int rc;
+  if (c->sw_dev) {
+    rc = N > 0 ? c->sw(c->sw_user, what, N, z, c->y, dv, d1, d2, ds, (void*)c->st) : 0;
+  } else {
+    if (c->swh_cap < N) {
+      sync(c);   // uploads from the old buffer
+      if (c->swh) HCK(hipHostFree(c->swh));
+      c->swh = nullptr;
+      c->swh_cap = 0;
+      HCK(hipHostMalloc((void**)&c->swh, 5 * (size_t)N * sizeof(double), hipHostMallocDefault));
+      c->swh_cap = N;
+    }
+    const int64_t hc = c->swh_cap;
+    double *hz = c->swh, *hv = hz + hc, *h1 = hv + hc, *h2 = h1 + hc, *hs = h2 + hc;
+    const double* hy = sw_host_y(c);
+    // (the stream is in order: the previous call's uploads from these buffers precede this download)
+    if (N > 0) d2h(c, hz, z, N);
+    sync(c);
+    rc = N > 0 ? c->sw(c->sw_user, what, N, hz, hy, hv, h1, h2, hs, nullptr) : 0;
+    if (rc == 0 && N > 0) {
+      if (what & SCS_SW_VALUE) h2d(c, dv, hv, N);
+      if (what & (SCS_SW_D1 | SCS_SW_GGN)) h2d(c, d1, h1, N);
+      if (what & (SCS_SW_D2 | SCS_SW_GGN)) h2d(c, d2, h2, N);
+      if (what & SCS_SW_GGN) h2d(c, ds, hs, N);
+    }
+  }
+  if (rc != 0) {
+    invalidate_caches(c);   // z was replaced, its value was not
+    fail(c, SCS_ERR_CALLBACK, "sample-wise loss callback (what = %d) returned %d", what, rc);
+  }
+  HCK(launch_samplewise_epilogue(need, dv, d1, d2, ds, N, Npad, c->gN, c->hN, c->wN, c->vN, c->valpart, c->st));
+}
+
 // Forward pass at the device vector xd whose host copy is xh: z = A x (or the
 // cached z), then the epilogue with `flags`.  Always refreshes the f-value
 // cache; returns f(x) (global).
@@ -1132,8 +1254,7 @@ double forward(scs_ctx* c, const double* xh, const double* xd, int flags, bool n
     const int ns = matvec_n(c, xd, c->nsplit);
     tend(c, T_GEMV, e0);
     flags |= EPI_Z | EPI_VAL;
-    HCK(launch_epilogue(c->loss, c->ggn, flags, c->zpart, ns, c->Npad, c->y, c->N, c->Npad, c->scale, c->z,
-                        c->gN, c->hN, c->wN, c->vN, c->valpart, c->st));
+    loss_epilogue(c, flags, c->zpart, ns, c->z);
     // loss sum -> scal[ZF_SLOT] (reduce buffer slot 0 in multi-rank); a slot of its own: the value
     // stays in flight until the next use (no host round trip when the caller only needs z)
     ensure_red(c);
@@ -1147,8 +1268,7 @@ double forward(scs_ctx* c, const double* xh, const double* xd, int flags, bool n
     c->zvalid = true;
   } else if (flags & ~(EPI_VAL | EPI_Z)) {
     flags &= ~(EPI_Z | EPI_VAL);
-    HCK(launch_epilogue(c->loss, c->ggn, flags, c->z, 1, c->Npad, c->y, c->N, c->Npad, c->scale, c->z, c->gN, c->hN,
-                        c->wN, c->vN, c->valpart, c->st));
+    loss_epilogue(c, flags, c->z, 1, c->z);
   }
   if (need_val && c->zf_pending) {
     sync(c);
@@ -1240,8 +1360,7 @@ void ftest_enqueue(scs_ctx* c, const double* xd) {
   ensure_red(c);   // sized by the data's view, before the held-out one is swapped in
   TestScope ts(c);
   const int ns = matvec_n(c, xd, c->nsplit);
-  HCK(launch_epilogue(c->loss, c->ggn, EPI_VAL, c->zpart, ns, c->Npad, c->y, c->N, c->Npad, c->scale, c->z, c->gN,
-                      c->hN, c->wN, c->vN, c->valpart, c->st));
+  loss_epilogue(c, EPI_VAL, c->zpart, ns, c->z);
   double* dst = sharded(c) ? c->red : c->scal + TF_SLOT;
   HCK(launch_sum_partials(c->valpart, c->nval, dst, c->st));
   allreduce(c, c->red, 1);
@@ -1334,7 +1453,7 @@ bool ls_incremental(const scs_ctx* c) {
   const char* e = std::getenv("SCS_LS_INCR");   // read per call (A/B within one process)
   const bool off = e && e[0] == '0';
   return !off && !c->generic && (c->loss == SCS_LOSS_LOGISTIC_MARGIN || c->loss == SCS_LOSS_LOGISTIC_CE ||
-                                 c->loss == SCS_LOSS_LEAST_SQUARES);
+                                 c->loss == SCS_LOSS_LEAST_SQUARES || c->loss == SCS_LOSS_SAMPLEWISE);
 }
 
 double line_search(scs_ctx* c, const double* xh, const double* xd, const double* dd) {
@@ -1363,8 +1482,7 @@ double line_search(scs_ctx* c, const double* xh, const double* xd, const double*
     tbegin(c, T_GEMV, &e0);
     const int ns = matvec_n(c, dd, c->nsplit);
     tend(c, T_GEMV, e0);
-    HCK(launch_epilogue(c->loss, c->ggn, EPI_Z, c->zpart, ns, c->Npad, c->y, c->N, c->Npad, c->scale, zd, nullptr,
-                        nullptr, nullptr, nullptr, c->valpart, c->st));
+    loss_epilogue(c, EPI_Z, c->zpart, ns, zd);
     ensure_red(c);
   }
   // the band (relative) within which an incremental trial is re-decided on the direct form;
@@ -1381,8 +1499,7 @@ double line_search(scs_ctx* c, const double* xh, const double* xd, const double*
     double ft;
     if (incr) {
       HCK(launch_ls_pair(c->z, zd, alpha, c->Npad, pair, c->st));
-      HCK(launch_epilogue(c->loss, c->ggn, EPI_VAL, pair, 2, c->Npad, c->y, c->N, c->Npad, c->scale, nullptr, nullptr,
-                          nullptr, nullptr, nullptr, c->valpart, c->st));
+      loss_epilogue(c, EPI_VAL, pair, 2, nullptr);   // (a sample-wise trial's z goes to scratch, not over c->z)
       double* dst = sharded(c) ? c->red : c->scal + 14;
       HCK(launch_sum_partials(c->valpart, c->nval, dst, c->st));
       allreduce(c, c->red, 1);
@@ -2084,6 +2201,7 @@ void ggn_sample_direction_sharded(scs_ctx* c, const double* xh) {
     c->gview_ok = false;
   }
   if (!held) {
+    ++c->y_stamp;   // the gathered view's y is refilled
     if (Npg * c->mpad + Npg > c->red_cap) fail(c, SCS_ERR_COMM, "reduce buffer too small for the row all-gather");
     // each local row at its global position: in the data (row0 + r) or in the selected batch
     std::vector<int64_t> rows(Ng, -1);
@@ -2590,6 +2708,9 @@ int scs_destroy(scs_ctx* c) {
   for (hipEvent_t e : c->loop_ev)
     if (e) (void)hipEventDestroy(e);
   if (c->cbh) (void)hipHostFree(c->cbh);
+  if (c->swh) (void)hipHostFree(c->swh);
+  for (auto& e : c->swy)
+    if (e.h) (void)hipHostFree(e.h);
   lu_aux_free(&c->lu);
   qr_aux_free(&c->qr);
   if (c->sf) {
@@ -3615,10 +3736,25 @@ int scs_has_test(scs_ctx* c, int* on) {
 }
 
 int scs_set_loss(scs_ctx* c, int loss, int ggn, double scale) {
+  if (is_group(c) && (loss == SCS_LOSS_SAMPLEWISE || ggn == SCS_GGN_SAMPLEWISE)) {
+    c->err = "a sample-wise loss takes a single-device context (a group's devices run one host thread each)";
+    return SCS_ERR_ARG;
+  }
   if (is_group(c)) return group_run(c, [&](scs_ctx* s_, int) { return scs_set_loss(s_, loss, ggn, scale); });
   return guarded(c, [&] {
-    if (loss < SCS_LOSS_LOGISTIC_MARGIN || loss > SCS_LOSS_CALLBACK) fail(c, SCS_ERR_ARG, "unknown loss %d", loss);
-    if (ggn < SCS_GGN_NONE || ggn > SCS_GGN_LINEAR_LS) fail(c, SCS_ERR_ARG, "unknown ggn kind %d", ggn);
+    if (loss < SCS_LOSS_LOGISTIC_MARGIN || loss > SCS_LOSS_SAMPLEWISE) fail(c, SCS_ERR_ARG, "unknown loss %d", loss);
+    if (ggn < SCS_GGN_NONE || ggn > SCS_GGN_SAMPLEWISE) fail(c, SCS_ERR_ARG, "unknown ggn kind %d", ggn);
+    if ((loss == SCS_LOSS_SAMPLEWISE) != (ggn == SCS_GGN_SAMPLEWISE) && !(loss == SCS_LOSS_SAMPLEWISE && ggn == SCS_GGN_NONE))
+      fail(c, SCS_ERR_ARG, "SCS_LOSS_SAMPLEWISE takes SCS_GGN_NONE or SCS_GGN_SAMPLEWISE, and no other loss takes the latter");
+    if (loss == SCS_LOSS_SAMPLEWISE) {
+      if (!c->sw) fail(c, SCS_ERR_STATE, "no sample-wise loss functions: call scs_set_loss_samplewise first");
+      if (scale != 1.0)
+        fail(c, SCS_ERR_ARG, "a sample-wise loss takes scale = 1 (its values arrive scaled), got %g", scale);
+      if (ggn == SCS_GGN_SAMPLEWISE && !c->sw_ggn)
+        fail(c, SCS_ERR_ARG, "SCS_GGN_SAMPLEWISE needs the GGN pieces (scs_set_loss_samplewise with has_ggn)");
+      if (c->has_data && c->generic)
+        fail(c, SCS_ERR_ARG, "a sample-wise loss needs device data (A, y): this context is a ProblemGeneric");
+    }
     if ((loss == SCS_LOSS_QUADRATIC || loss == SCS_LOSS_ROSENBROCK || loss == SCS_LOSS_CALLBACK) && sharded(c))
       fail(c, SCS_ERR_ARG, "quadratic / Rosenbrock / callback problems are not row-sharded");
     if (loss == SCS_LOSS_CALLBACK && (!c->has_data || !c->generic))
@@ -3633,6 +3769,22 @@ int scs_set_loss(scs_ctx* c, int loss, int ggn, double scale) {
     c->scale = scale;
     c->loss_set = true;
     ++c->data_gen;
+    invalidate_caches(c);
+  });
+}
+
+int scs_set_loss_samplewise(scs_ctx* c, scs_samplewise_fn* fn, void* user, int device_ptrs, int has_ggn) {
+  if (is_group(c)) {
+    c->err = "a sample-wise loss takes a single-device context (a group's devices run one host thread each)";
+    return SCS_ERR_ARG;
+  }
+  return guarded(c, [&] {
+    if (!fn && c->loss_set && c->loss == SCS_LOSS_SAMPLEWISE)
+      fail(c, SCS_ERR_STATE, "the sample-wise loss is in use: select another loss before removing its functions");
+    c->sw = fn;
+    c->sw_user = user;
+    c->sw_dev = device_ptrs != 0;
+    c->sw_ggn = has_ggn != 0;
     invalidate_caches(c);
   });
 }
@@ -4194,7 +4346,8 @@ int scs_iterate_ex(scs_ctx* c, const double* x0, const double* x_star, int64_t m
       const char* fz = std::getenv("SCS_LQN_FUSED");
       const bool fused = c->method == SCS_PROX_LQNSCORE && c->ss_type == 1 && m >= 16384 && !sharded(c) &&
                          c->smooth != SCS_SMOOTH_PHUBER_GL && c->smooth != SCS_SMOOTH_OSBA_GL &&
-                         !(c->use_prox && c->reg == SCS_REG_GL) && c->reg != SCS_REG_GL && !(fz && fz[0] == '0');
+                         !(c->use_prox && c->reg == SCS_REG_GL) && c->reg != SCS_REG_GL && !(fz && fz[0] == '0') &&
+                         c->loss != SCS_LOSS_SAMPLEWISE;   // its epoch is pipelined past the caller's functions
       if (fused) {
         const double Mg = get_Mg(c, c->Mh, c->nu, c->mu, m);
         const double step = c->has_L ? jl_min_h(1 / c->L, 1.0) : 0.5;

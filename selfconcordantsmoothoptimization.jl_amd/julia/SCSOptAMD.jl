@@ -15,7 +15,7 @@ using SelfConcordantSmoothOptimization
 import SelfConcordantSmoothOptimization: step!, init!, ProximalMethod, ProxModel, is_interval_set
 
 export DeviceProblem, configure!, iterate_device!, set_gram_cache!, set_solver!, rccl_unique_id, set_comm_rccl!,
-       set_comm_callback!, set_test!, set_test_device!, set_compute_f32!, fallback_counts, data_info
+       set_comm_callback!, set_test!, set_test_device!, set_compute_f32!, fallback_counts, data_info, samplewise
 
 const lib = joinpath(@__DIR__, "..", "scsopt", "libscsopt.so")
 
@@ -38,6 +38,87 @@ function chk(rc::Integer, ctx::Ptr{Cvoid})
     end
     msg = unsafe_string(ccall((:scs_last_error, lib), Cstring, (Ptr{Cvoid},), ctx))
     error(msg)   # SCS_ERR_REF carries the reference's own Base.error text
+end
+
+# ---- sample-wise losses outside the menu: f(A, y, x) = Σᵢ ℓ(yᵢ, aᵢᵀx) (SCS_LOSS_SAMPLEWISE) ----------
+# A, y and every product with A stay on the device (any DeviceProblem door, row shards, minibatches,
+# held-out rows); the caller's elementwise functions see z = A*x and y of the view in use.
+#   host mode (device = false): value(z, y), d1(z, y), d2(z, y); link(z) = ŷ, link_d1(z), grad_fy(y, ŷ),
+#     hess_fy(y, ŷ) (the diagonal) on Vector{Float64} views of the library's pinned buffers; each returns
+#     n numbers (or a scalar, broadcast).
+#   device mode (device = true): the same names receive the library's DEVICE pointers and its stream and
+#     queue their own kernels on it: value(out, z, y, n, stream), d1(...), d2(...); link(ŷ_out, z, n, stream),
+#     link_d1(s_out, z, n, stream), grad_fy(out, y, ŷ, n, stream), hess_fy(out, y, ŷ, n, stream).  Nothing
+#     is synchronised around the call.
+# Pass it where a loss Symbol goes: DeviceProblem(A, y, x0, samplewise(value; d1, d2), λ; ...).  No
+# automatic differentiation: ProxLQNSCORE needs d1, ProxNSCORE d1 and d2, ProxGGNSCORE the four GGN pieces.
+mutable struct Samplewise   # mutable: `user` is pointer_from_objref(sw), rooted by the model
+    value::Function
+    d1::Union{Function,Nothing}
+    d2::Union{Function,Nothing}
+    link::Union{Function,Nothing}
+    link_d1::Union{Function,Nothing}
+    grad_fy::Union{Function,Nothing}
+    hess_fy::Union{Function,Nothing}
+    device::Bool
+end
+
+function samplewise(value::Function, d1=nothing, d2=nothing; link=nothing, link_d1=nothing, grad_fy=nothing,
+                    hess_fy=nothing, device::Bool=false)
+    ggn = (link, link_d1, grad_fy, hess_fy)
+    (any(isnothing, ggn) && !all(isnothing, ggn)) &&
+        error("samplewise: link, link_d1, grad_fy and hess_fy go together (ProxGGNSCORE needs all four)")
+    return Samplewise(value, d1, d2, link, link_d1, grad_fy, hess_fy, device)
+end
+
+has_ggn(sw::Samplewise) = all(!isnothing, (sw.link, sw.link_d1, sw.grad_fy, sw.hess_fy))
+const LossSpec = Union{Symbol,Samplewise}
+
+function samplewise_trampoline(user::Ptr{Cvoid}, what::Cint, n::Int64, zp::Ptr{Float64}, yp::Ptr{Float64},
+                               vp::Ptr{Float64}, d1p::Ptr{Float64}, d2p::Ptr{Float64}, sp::Ptr{Float64},
+                               stream::Ptr{Cvoid})::Cint
+    sw = unsafe_pointer_to_objref(user)::Samplewise
+    noad = " (no automatic differentiation on the device path)"
+    try
+        (what & 2) != 0 && sw.d1 === nothing && error("this method needs d1" * noad)
+        (what & 4) != 0 && sw.d2 === nothing && error("ProxNSCORE needs d2" * noad)
+        (what & 8) != 0 && !has_ggn(sw) && error("ProxGGNSCORE needs link, link_d1, grad_fy and hess_fy" * noad)
+        if sw.device
+            (what & 1) != 0 && sw.value(vp, zp, yp, n, stream)
+            (what & 2) != 0 && sw.d1(d1p, zp, yp, n, stream)
+            (what & 4) != 0 && sw.d2(d2p, zp, yp, n, stream)
+            if (what & 8) != 0        # ŷ rests in the s area until r and q are formed from it
+                sw.link(sp, zp, n, stream)
+                sw.grad_fy(d1p, yp, sp, n, stream)
+                sw.hess_fy(d2p, yp, sp, n, stream)
+                sw.link_d1(sp, zp, n, stream)
+            end
+        else
+            z, y = unsafe_wrap(Array, zp, n), unsafe_wrap(Array, yp, n)
+            (what & 1) != 0 && (unsafe_wrap(Array, vp, n) .= sw.value(z, y))
+            (what & 2) != 0 && (unsafe_wrap(Array, d1p, n) .= sw.d1(z, y))
+            (what & 4) != 0 && (unsafe_wrap(Array, d2p, n) .= sw.d2(z, y))
+            if (what & 8) != 0
+                ŷ = sw.link(z)
+                unsafe_wrap(Array, sp, n) .= sw.link_d1(z)
+                unsafe_wrap(Array, d1p, n) .= sw.grad_fy(y, ŷ)
+                unsafe_wrap(Array, d2p, n) .= sw.hess_fy(y, ŷ)
+            end
+        end
+        return Cint(0)
+    catch err
+        CB_EXCEPTION[] = err
+        return Cint(1)
+    end
+end
+
+# register sw with the context; returns the (loss, ggn) kinds scs_set_loss takes
+function bind_samplewise(ctx::Ptr{Cvoid}, sw::Samplewise)
+    fp = @cfunction(samplewise_trampoline, Cint, (Ptr{Cvoid}, Cint, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                                                  Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}))
+    chk(ccall((:scs_set_loss_samplewise, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint),
+              ctx, fp, pointer_from_objref(sw), sw.device ? 1 : 0, has_ggn(sw) ? 1 : 0), ctx)
+    return 7, (has_ggn(sw) ? 3 : 0)
 end
 
 mutable struct DeviceProblem <: ProxModel
@@ -84,9 +165,15 @@ function create_ctx(device::Integer, devices=nothing, device_exchange::Symbol=:r
 end
 
 function finish_problem(ctx, A, yv, x0, loss, λ, out_fn, scale, L, sol, C_set, P)
-    chk(ccall((:scs_set_loss, lib), Cint, (Ptr{Cvoid}, Cint, Cint, Float64), ctx, LOSS[loss], GGN[out_fn], scale), ctx)
+    if loss isa Samplewise   # its values arrive scaled (`scale` is not applied) and it carries its own GGN pieces
+        out_fn === nothing || error("a sample-wise loss carries its own GGN pieces: no out_fn")
+        lk, gk = bind_samplewise(ctx, loss)
+        chk(ccall((:scs_set_loss, lib), Cint, (Ptr{Cvoid}, Cint, Cint, Float64), ctx, lk, gk, 1.0), ctx)
+    else
+        chk(ccall((:scs_set_loss, lib), Cint, (Ptr{Cvoid}, Cint, Cint, Float64), ctx, LOSS[loss], GGN[out_fn], scale), ctx)
+    end
     model = DeviceProblem(ctx, A, yv, x0, nothing, λ, nothing, nothing, L, sol, C_set, P, out_fn,
-                          nothing, nothing, nothing, nothing, nothing, nothing)
+                          loss isa Samplewise ? loss : nothing, nothing, nothing, nothing, nothing, nothing)
     # optim_loop! calls model.f(model.A, model.y, x) and, with held-out data, ftest(x) =
     # model.f(model.Atest, model.ytest, x) (iterate.jl:168,173): both evaluate on the device
     model.f = (A_, y_, x) -> (A_ !== nothing && A_ === model.Atest) ? devftest(model, x) : devf(model, x)
@@ -144,7 +231,7 @@ end
 # Problem(A, y, x0, f, λ; ...) (problems.jl:61-81) with A on the device.  Row sharding: pass
 # the local rows with N_global / row0, and attach a communicator (set_comm_rccl! /
 # set_comm_callback!) before the first step.
-function DeviceProblem(A::Matrix{Float64}, y::AbstractVector, x0::Vector{Float64}, loss::Symbol, λ;
+function DeviceProblem(A::Matrix{Float64}, y::AbstractVector, x0::Vector{Float64}, loss::LossSpec, λ;
                        out_fn::Union{Symbol,Nothing}=nothing, scale::Float64=1.0 / size(A, 1),
                        L=nothing, sol::Vector{Float64}=zero(x0), C_set=nothing, P=nothing, device::Integer=0,
                        N_global::Integer=size(A, 1), row0::Integer=0, devices=nothing,
@@ -164,7 +251,7 @@ end
 # promotes every product to Float64): the rows are stored as fp32 on the device as they are -- half
 # the memory of A, fp64 arithmetic, bit for bit what Float64.(A) gives (scs_set_data_f32).  An
 # Atest::Matrix{Float32} is stored the same way; any other dense Atest is rounded to fp32 on the device.
-function DeviceProblem(A::Matrix{Float32}, y::AbstractVector, x0::Vector{Float64}, loss::Symbol, λ;
+function DeviceProblem(A::Matrix{Float32}, y::AbstractVector, x0::Vector{Float64}, loss::LossSpec, λ;
                        out_fn::Union{Symbol,Nothing}=nothing, scale::Float64=1.0 / size(A, 1),
                        L=nothing, sol::Vector{Float64}=zero(x0), C_set=nothing, P=nothing, device::Integer=0,
                        N_global::Integer=size(A, 1), row0::Integer=0, devices=nothing,
@@ -197,7 +284,7 @@ function device_y(y::AbstractVector, N)
 end
 
 function DeviceProblem(ptr::Ptr{Cvoid}, N::Integer, m::Integer, y::Union{AbstractVector,Ptr{Cvoid}},
-                       x0::Vector{Float64}, loss::Symbol, λ;
+                       x0::Vector{Float64}, loss::LossSpec, λ;
                        elem::Type=Float64, strides::Tuple{Integer,Integer}=(1, N), dense_f32::Bool=false,
                        stream::Ptr{Cvoid}=C_NULL,
                        out_fn::Union{Symbol,Nothing}=nothing, scale::Float64=1.0 / N,
@@ -238,7 +325,7 @@ end
 
 # A::SparseMatrixCSC (README.md:105 builds it with sprandn): its CSC arrays are the column copy;
 # the row copy is the CSC of the transpose.  0-based indices on the C side.
-function DeviceProblem(A::SparseMatrixCSC{Float64}, y::AbstractVector, x0::Vector{Float64}, loss::Symbol, λ;
+function DeviceProblem(A::SparseMatrixCSC{Float64}, y::AbstractVector, x0::Vector{Float64}, loss::LossSpec, λ;
                        out_fn::Union{Symbol,Nothing}=nothing, scale::Float64=1.0 / size(A, 1),
                        L=nothing, sol::Vector{Float64}=zero(x0), C_set=nothing, P=nothing, device::Integer=0,
                        val_f32::Bool=false, N_global::Integer=size(A, 1), row0::Integer=0, Atest=nothing,
@@ -272,7 +359,7 @@ val_width(T::Type) = (T === Float32 || T === Float64) ? Cint(sizeof(T)) :
                      throw(ArgumentError("elem is Float64 or Float32"))
 
 function DeviceProblem(rowptr::Ptr{Cvoid}, colidx::Ptr{Cvoid}, val::Ptr{Cvoid}, N::Integer, m::Integer,
-                       nnz::Integer, y::Union{AbstractVector,Ptr{Cvoid}}, x0::Vector{Float64}, loss::Symbol, λ;
+                       nnz::Integer, y::Union{AbstractVector,Ptr{Cvoid}}, x0::Vector{Float64}, loss::LossSpec, λ;
                        ptr_type::Type=Int64, idx_type::Type=Int32, elem::Type=Float64, val_f32::Bool=false,
                        stream::Ptr{Cvoid}=C_NULL,
                        out_fn::Union{Symbol,Nothing}=nothing, scale::Float64=1.0 / N,

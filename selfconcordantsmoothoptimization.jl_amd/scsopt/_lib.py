@@ -21,8 +21,11 @@ SCS_MULTI_HOST_EXCHANGE = 1   # scs_create_multi_ex flag
 SCS_CB_F, SCS_CB_GRAD, SCS_CB_HESS, SCS_CB_GGN, SCS_CB_FTEST, SCS_CB_GRAD_X = range(6)
 SCS_CB_NO_METHOD = 2   # a callback's answer to SCS_CB_GRAD_X when grad_fx takes no single argument
 
-LOSS = {"logistic_margin": 1, "logistic_ce": 2, "least_squares": 3, "quadratic": 4, "rosenbrock": 5, "callback": 6}
-GGN = {None: 0, "sigmoid_ce": 1, "linear_ls": 2}
+SCS_SW_VALUE, SCS_SW_D1, SCS_SW_D2, SCS_SW_GGN = 1, 2, 4, 8   # scs_samplewise_fn's `what` bits
+
+LOSS = {"logistic_margin": 1, "logistic_ce": 2, "least_squares": 3, "quadratic": 4, "rosenbrock": 5, "callback": 6,
+        "samplewise": 7}
+GGN = {None: 0, "sigmoid_ce": 1, "linear_ls": 2, "samplewise": 3}
 REG = {"l1": 1, "l2": 2, "indbox": 3, "gl": 4}
 SMOOTH = {"phuber_l1l2": 1, "phuber_indbox": 2, "phuber_gl": 3, "exp_indbox": 4, "logexp_indbox": 5, "osba_l1l2": 6,
           "osba_gl": 7}
@@ -68,6 +71,9 @@ c_i64p = C.POINTER(C.c_int64)
 c_i32p = C.POINTER(C.c_int32)
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
 LOSS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, c_dp, C.c_int64, c_dp)
+# (user, what, n, z, y, val, d1, d2, s, stream): plain addresses, host or device (scs_set_loss_samplewise)
+SAMPLEWISE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                            C.c_void_p, C.c_void_p, C.c_void_p)
 
 
 class Synth(C.Structure):
@@ -141,6 +147,7 @@ _SIGS = {
                                              C.c_int64]),
     "scs_set_loss": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double]),
     "scs_set_loss_callback": (C.c_int, [C.c_void_p, LOSS_FN, C.c_void_p, C.c_int64]),
+    "scs_set_loss_samplewise": (C.c_int, [C.c_void_p, SAMPLEWISE_FN, C.c_void_p, C.c_int, C.c_int]),
     "scs_set_reg": (C.c_int, [C.c_void_p, C.c_int, c_dp, C.c_int, c_dp, c_dp, C.c_int64, c_i64p, C.c_int64]),
     "scs_set_smoother": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, c_dp, c_dp,
                                    C.c_int64]),
@@ -276,6 +283,20 @@ def parse_device_vector(iface, n):
     if strides is not None and n > 1 and int(strides[0]) != 8:
         raise ValueError("a device y must be contiguous")
     return int(iface["data"][0] or 0)
+
+
+class DeviceVector:
+    """n contiguous float64 at a device address, as __cuda_array_interface__ (version 2; stream None:
+    the consumer orders its own work) -- what torch.as_tensor reads to alias the library's buffers
+    for a device-mode sample-wise loss.  It owns nothing: the buffer belongs to the context.  (The
+    read-only flag stays False, the only value torch accepts; z and y are inputs by contract.)"""
+
+    def __init__(self, ptr, n):
+        self.ptr, self.n = int(ptr), int(n)
+
+    @property
+    def __cuda_array_interface__(self):
+        return {"shape": (self.n,), "typestr": "<f8", "data": (self.ptr, False), "version": 2, "strides": None}
 
 
 def _is_torch_tensor(a):

@@ -86,6 +86,51 @@ def callback(f, grad_fx=None, hess_fx=None, *, out_fn=None, jac_yx=None, grad_fy
     return CallbackLoss("callback", 1.0, f, grad_fx, hess_fx, out_fn, jac_yx, grad_fy, hess_fy)
 
 
+@dataclass(frozen=True, eq=False)
+class SamplewiseLoss(Loss):
+    """f(A, y, x) = Σᵢ ℓ(yᵢ, aᵢᵀx) with the caller's elementwise ℓ and derivatives
+    (SCS_LOSS_SAMPLEWISE): A, y and every product with A stay on the device."""
+    value: Optional[Callable] = field(default=None, repr=False)
+    d1: Optional[Callable] = field(default=None, repr=False)
+    d2: Optional[Callable] = field(default=None, repr=False)
+    link: Optional[Callable] = field(default=None, repr=False)
+    link_d1: Optional[Callable] = field(default=None, repr=False)
+    grad_fy: Optional[Callable] = field(default=None, repr=False)
+    hess_fy: Optional[Callable] = field(default=None, repr=False)
+    device: bool = False
+
+    @property
+    def has_ggn(self):
+        return None not in (self.link, self.link_d1, self.grad_fy, self.hess_fy)
+
+
+def samplewise(value, d1=None, d2=None, *, link=None, link_d1=None, grad_fy=None, hess_fy=None,
+               device=False) -> SamplewiseLoss:
+    """A loss outside the menu of the form f(A, y, x) = Σᵢ ℓ(yᵢ, zᵢ), z = A*x (Poisson, Huber, squared
+    hinge, probit, any GLM), usable wherever a menu kind is: the device keeps A (dense fp64 / fp32,
+    sparse, device arrays, row shards, minibatches, held-out rows) and every product with it; the
+    callables see z and y and return one number per sample.
+      value(z, y) -> ℓ(yᵢ, zᵢ) (scaled as f is: no scale is applied), d1(z, y) -> ∂ℓ/∂z,
+      d2(z, y) -> ∂²ℓ/∂z²;
+      for ProxGGNSCORE ŷᵢ = φ(zᵢ), f = Σ ℓ(yᵢ, ŷᵢ): link(z) -> ŷ, link_d1(z) -> dŷ/dz,
+      grad_fy(y, ŷ) -> ∂f/∂ŷ, hess_fy(y, ŷ) -> ∂²f/∂ŷ² (the diagonal of hess_fy), all four or none.
+    There is no automatic differentiation on the device path: ProxLQNSCORE (and every ∇f) needs d1,
+    ProxNSCORE d1 and d2, ProxGGNSCORE the four GGN pieces (d1 as well for its line search).
+    device=False: the callables get NumPy arrays (z crosses to the host per call, y once per view).
+    device=True: they get torch tensors that alias the library's device buffers, on the context's
+    stream (torch imported before scsopt); nothing crosses, the library does not synchronise."""
+    if not callable(value):
+        raise TypeError("samplewise(value, ...): value(z, y) must be callable")
+    for name, fn in (("d1", d1), ("d2", d2), ("link", link), ("link_d1", link_d1), ("grad_fy", grad_fy),
+                     ("hess_fy", hess_fy)):
+        if fn is not None and not callable(fn):
+            raise TypeError(f"samplewise: {name} must be callable or None")
+    ggn = (link, link_d1, grad_fy, hess_fy)
+    if any(g is not None for g in ggn) and any(g is None for g in ggn):
+        raise ValueError("samplewise: link, link_d1, grad_fy and hess_fy go together (ProxGGNSCORE needs all four)")
+    return SamplewiseLoss("samplewise", 1.0, value, d1, d2, link, link_d1, grad_fy, hess_fy, bool(device))
+
+
 def sigmoid_ce(scale: float = 1.0) -> OutFn:
     """Mfunc(A,x) = 1 ./ (1 .+ exp.(-A*x)) with f(y,ŷ) = -scale*sum(y.*log.(ŷ) .+ (1 .- y).*log.(1 .- ŷ))
     (test/test_algs.jl:10-11, README.md:135-139)."""

@@ -38,6 +38,15 @@ def _accepts_one_arg(fn):
     return True
 
 
+def _samplewise_put_host(dst, src, name):
+    """A host-mode sample-wise callable's result into the library's output area: n numbers, or a
+    scalar (broadcast); anything else raises (the device mode applies the same rule through copy_)."""
+    src = np.asarray(src, dtype=np.float64)
+    if src.ndim != 0 and src.shape != dst.shape:
+        raise ValueError(f"samplewise: {name} returned shape {src.shape}, expected {dst.shape}")
+    dst[...] = src
+
+
 @dataclass
 class GetP:
     """get_P(n, G, ind) (prox-reg-utils.jl:9-62): group structure for "gl".
@@ -174,6 +183,14 @@ class Problem:
         if out_fn is not None and out_fn.scale != f.scale:
             raise ValueError("f and out_fn must use the same scale (one device loss scale)")
         scale = f.scale
+        if f.kind == "samplewise":
+            if self.generic:
+                raise ValueError("a sample-wise loss needs data: Problem(A, y, x0, samplewise(...), λ)")
+            if out_fn is not None:
+                raise ValueError("a sample-wise loss carries its own GGN pieces (link, link_d1, grad_fy, hess_fy): "
+                                 "no out_fn")
+            self._bind_samplewise(f)
+            ggn = "samplewise" if f.has_ggn else None
         self.ctx.check(_lib.lib.scs_set_loss(self.ctx.h, LOSS[f.kind], GGN[ggn], scale))
         self._cb_test = None
         if f.kind == "callback":
@@ -428,6 +445,79 @@ class Problem:
         cb = _lib.LOSS_FN(call)
         self.ctx._keep.append(cb)
         self.ctx.check(_lib.lib.scs_set_loss_callback(self.ctx.h, cb, None, nout))
+
+    def _bind_samplewise(self, f):
+        """Register a losses.samplewise(...) with scs_set_loss_samplewise.  The library hands over z and
+        y of the view in use (n entries) and the output areas it wants filled: NumPy views of its pinned
+        host buffers, or -- f.device -- torch tensors aliasing its device buffers, with the callables
+        run on the context's stream.  A Python exception inside a call is kept and re-raised by
+        Context.check."""
+        ctx = self.ctx
+        noad = ": the device path has no automatic differentiation (the reference's ForwardDiff default)"
+
+        def need(fn, name, who="this method"):
+            if fn is None:
+                raise ValueError(f"{who} needs {name}{noad}")
+            return fn
+
+        if f.device:
+            _lib.require_torch_runtime("a device-mode sample-wise loss")
+            import torch
+            dev = torch.device("cuda", ctx.device)
+
+            def wrap(p, n, readonly=False):
+                return torch.as_tensor(_lib.DeviceVector(p, n), device=dev)
+
+            def put(dst, src, name):
+                src = torch.as_tensor(src, dtype=torch.float64, device=dev)
+                if src.dim() != 0 and tuple(src.shape) != tuple(dst.shape):
+                    raise ValueError(f"samplewise: {name} returned shape {tuple(src.shape)}, expected "
+                                     f"{tuple(dst.shape)}")
+                dst.copy_(src)
+
+            def on_stream(stream):
+                s = torch.cuda.ExternalStream(int(stream), device=dev) if stream else torch.cuda.default_stream(dev)
+                return torch.cuda.stream(s)
+        else:
+            import contextlib
+
+            def wrap(p, n, readonly=False):
+                a = np.ctypeslib.as_array(C.cast(p, _lib.c_dp), shape=(n,))
+                if readonly:
+                    a.flags.writeable = False
+                return a
+
+            put = _samplewise_put_host
+
+            def on_stream(stream):
+                return contextlib.nullcontext()
+
+        def call(user, what, n, zp, yp, vp, d1p, d2p, sp, stream):
+            try:
+                n = int(n)
+                with on_stream(stream):
+                    z, y = wrap(zp, n, True), wrap(yp, n, True)
+                    if what & _lib.SCS_SW_VALUE:
+                        put(wrap(vp, n), f.value(z, y), "value")
+                    if what & _lib.SCS_SW_D1:
+                        put(wrap(d1p, n), need(f.d1, "d1")(z, y), "d1")
+                    if what & _lib.SCS_SW_D2:
+                        put(wrap(d2p, n), need(f.d2, "d2", "ProxNSCORE")(z, y), "d2")
+                    if what & _lib.SCS_SW_GGN:
+                        for nm in ("link", "link_d1", "grad_fy", "hess_fy"):
+                            need(getattr(f, nm), nm, "ProxGGNSCORE")
+                        yhat = f.link(z)
+                        put(wrap(sp, n), f.link_d1(z), "link_d1")
+                        put(wrap(d1p, n), f.grad_fy(y, yhat), "grad_fy")
+                        put(wrap(d2p, n), f.hess_fy(y, yhat), "hess_fy")
+                return 0
+            except BaseException as e:   # noqa: BLE001 -- handed back to the caller by Context.check
+                ctx._cb_exc = e
+                return 1
+
+        cb = _lib.SAMPLEWISE_FN(call)
+        ctx._keep.append(cb)
+        ctx.check(_lib.lib.scs_set_loss_samplewise(ctx.h, cb, None, 1 if f.device else 0, 1 if f.has_ggn else 0))
 
     @classmethod
     def synthetic(cls, N, m, x0, f, lam, *, kind=1, seed=1234, density=0.1, out_fn=None, device=0,
