@@ -631,6 +631,9 @@ hipError_t gram_launch_gen(const double* A1, int64_t lda1, const double* A2, int
 // global loads have a whole iteration to land, and the MFMA order per
 // accumulator is the plain loop's (p, u) order: G is bitwise identical to
 // gram_f64_kernel / gram_glds_kernel of the same tile height.
+// The staging loads of the panel-blocked forms are raw buffer loads from scalar bases
+// (gram_sia_body.h SB: no per-lane address arithmetic in the K loop); PIPE bit 16 keeps the
+// per-lane pointers, as do the CM forms (run-time stride), the persistent BND ones among them.
 // CM: column-major operands (the Cholesky's trailing updates, gen form with A1 == A2),
 // S = leading dimension; stage k of feature f is the 16 samples at f * S + k0 + 16 k.
 // AV: the same pass also forms Aᵀv (the Jᵀr / ∇f product of the step, SURVEY §8d "one fused
@@ -696,6 +699,13 @@ int gram_tall_mode() {
   static const int v = env_int("SCS_GRAM_GLDS", 3);
   return v;
 }
+//   SCS_GRAM_ADDR (fp64 256 x 128 interleaved kernels): unset/1 = staging loads from scalar bases
+//                 (gram_sia_body.h SB), 0 = the per-lane 64-bit addresses they had before, with the
+//                 default barrier-edge order whatever SCS_GRAM_SIA says (gram_sia_kernel<26, 4, ...>).
+int gram_addr_mode() {
+  static const int v = env_int("SCS_GRAM_ADDR", 1);
+  return v;
+}
 //   SCS_GRAM_DIAGPAIR (256 x 128 tiles): unset/1 = the unpacked launches' list pairs the diagonal's
 //                 D1 blocks (gram_tiles.h; the interleaved kernels only), 0 = the [U; D1] tiles.
 int gram_pair_ok() {
@@ -737,7 +747,8 @@ template <bool AV, class... Args>
 static void sia_tall_launch(unsigned grid, hipStream_t st, Args... args) {
   static thread_local char name[64];
   int pipe = 1;
-  switch (gram_edge_bits()) {
+  switch (gram_addr_mode() ? gram_edge_bits() : 16) {
+    case 16: pipe = 26; hipLaunchKernelGGL((gram_sia_kernel<26, 4, false, AV>), dim3(grid), dim3(512), 0, st, args...); break;
     case 2: pipe = 10; hipLaunchKernelGGL((gram_sia_kernel<10, 4, false, AV>), dim3(grid), dim3(512), 0, st, args...); break;
     case 4: pipe = 12; hipLaunchKernelGGL((gram_sia_kernel<12, 4, false, AV>), dim3(grid), dim3(512), 0, st, args...); break;
     default: hipLaunchKernelGGL((gram_sia_kernel<1, 4, false, AV>), dim3(grid), dim3(512), 0, st, args...);

@@ -20,7 +20,9 @@
   //          it before lgkmcnt(0), not the barrier);
   //   2 (E2) phase 2a head: one MFMA group ahead of the vmcnt wait, the w products and the addresses;
   //   4 (E3) phase 2a tail: each ds_write ahead of its MFMA group.
-  constexpr bool E1 = PIPE >= 8 && (PIPE & 1), E2 = PIPE >= 8 && (PIPE & 2), E3 = PIPE >= 8 && (PIPE & 4);
+  // PIPE bit 16 (with 8 + bits) keeps the staging loads on per-lane 64-bit addresses (SB below).
+  constexpr int EP = PIPE & 15;
+  constexpr bool E1 = EP >= 8 && (EP & 1), E2 = EP >= 8 && (EP & 2), E3 = EP >= 8 && (EP & 4);
   // pair items (gram_tiles.h: the D1 blocks of two row blocks in one 256 x 128 tile) are decoded by
   // the panel-blocked 256 x 128 kernels; their A2 stage block is the A1 block times w (256 rows)
   constexpr bool PAIRT = TI == 4 && !CM && !BND;
@@ -89,6 +91,30 @@ bnd_tile:
                       : A + ((int64_t)bj * S + st0) * GT * GBK + sf0 * GBK + 2 * sc;
   const double* srcW = w + k0 + 2 * sc;
   const double* srcV = AV ? v + k0 + 2 * sc : nullptr;
+  // SB, the panel-blocked kernels' staging: nothing in a staging address differs between the lanes
+  // from stage to stage, so the 64-bit bases of the tile (panels pa, pb, bj, w, v at stage st0) stay
+  // in SGPRs and advance by scalar adds, each load is a raw buffer load through a descriptor built
+  // on its stage window (one 128 x 16 block of a panel; 128 B of w / v), and a lane adds one
+  // constant 32-bit byte offset (vo for A, vw for w / v) and the chunk's uniform offset (soffset).
+  // No offset grows with K: a panel passes 4 GiB above 4 M rows.  The loop then holds no VALU
+  // address arithmetic; the values loaded, and all that follows them, are the pointer form's.  The
+  // bases pass through readfirstlane, so that no load is wrapped in a waterfall loop.
+  constexpr bool SB = !CM && !(PIPE & 16);
+  constexpr int STB = GT * GBK * (int)sizeof(TA);   // bytes of one panel's stage block
+  auto uni = [](const void* p) {
+    const uint64_t x = (uint64_t)p;
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)x), hi = __builtin_amdgcn_readfirstlane((uint32_t)(x >> 32));
+    return (const char*)((uint64_t)hi << 32 | lo);
+  };
+  const char* const ubA = SB ? uni(A + ((int64_t)pa * S + st0) * GT * GBK) : nullptr;
+  const char* const ubP = SB ? uni(A + ((int64_t)pb * S + st0) * GT * GBK) : nullptr;
+  const char* const ubB = SB ? uni(A + ((int64_t)bj * S + st0) * GT * GBK) : nullptr;
+  const char* const ubW = SB ? uni(w + k0) : nullptr;
+  const char* const ubV = SB && AV ? uni(v + k0) : nullptr;
+  const int vo = (sf0 * GBK + 2 * sc) * (int)sizeof(TA), vw = 2 * sc * (int)sizeof(double);
+  auto window = [](const char* p, int bytes) {   // 0x00020000: the gfx9 raw-buffer word 3
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p), 0, bytes, 0x00020000);
+  };
   double* la = lds;
   double* lb = lds + GTI * GBK;
   int woff[NA];
@@ -115,6 +141,27 @@ bnd_tile:
       for (int i = 0; i < NA; ++i) ra[i] = *(const PR*)(srcA + st * GBK + (int64_t)FS * i * S);
 #pragma unroll
       for (int i = 0; i < NB; ++i) rb[i] = *(const PR*)(srcB + st * GBK + (int64_t)FS * i * SB2);
+    } else if constexpr (SB) {
+      auto bload = [](auto d, int voff, int soff) {   // b128 for fp64 pairs, b64 for fp32 pairs
+        if constexpr (sizeof(PR) == 16) return __builtin_bit_cast(PR, __builtin_amdgcn_raw_buffer_load_b128(d, voff, soff, 0));
+        else return __builtin_bit_cast(PR, __builtin_amdgcn_raw_buffer_load_b64(d, voff, soff, 0));
+      };
+      const int64_t so = st * STB;
+      const auto da = window(ubA + so, STB), dp = window(ubP + so, STB);
+#pragma unroll
+      for (int i = 0; i < NA; ++i) {
+        const int f = FS * i;   // + sf0 (in vo): the panel of f is f / 128 (FS divides 128)
+        ra[i] = bload((f >> 7) ? dp : da, vo, (f & 127) * GBK * (int)sizeof(TA));
+      }
+      if (!PT) {
+        const auto db = window(ubB + so, STB);
+#pragma unroll
+        for (int i = 0; i < NB; ++i) rb[i] = bload(db, vo, FS * GBK * i * (int)sizeof(TA));
+      }
+      constexpr int WB = GBK * (int)sizeof(double);
+      rw = __builtin_bit_cast(v2d, __builtin_amdgcn_raw_buffer_load_b128(window(ubW + st * WB, WB), vw, 0, 0));
+      if (FA) rv = __builtin_bit_cast(v2d, __builtin_amdgcn_raw_buffer_load_b128(window(ubV + st * WB, WB), vw, 0, 0));
+      return;
     } else {
       const int64_t so = st * GT * GBK;
 #pragma unroll
