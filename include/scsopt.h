@@ -464,10 +464,31 @@ int scs_eval_reg(scs_ctx* ctx, const double* x, double* gval);
  * the inner `for (i, sample) in enumerate(data)` loop over the registered
  * list; scs_select_batch(b) makes batch b the As, ys of the following scs_step
  * calls (b = -1: the full data).  f / get_reg / the histories always use the
- * full data (iterate.jl:168).  nbatch = 0 clears the list.  One rank; a
- * sparse A's batches are gathered dense (the reference's Matrix(As')).                                                                          */
+ * full data (iterate.jl:168).  nbatch = 0 clears the list and frees every
+ * batch view.  On several ranks the list holds GLOBAL rows: every rank passes
+ * the same list and keeps the rows it owns (possibly none of a batch).  A
+ * sparse A's batches are gathered dense (the reference's Matrix(As')) unless
+ * scs_set_sparse_batches keeps them sparse.                                 */
 int scs_set_batches(scs_ctx* ctx, const int64_t* rows, const int64_t* offsets, int64_t nbatch);
 int scs_select_batch(scs_ctx* ctx, int64_t b);
+/* Opt-in (default 0): under ProxLQNSCORE a minibatch of a sparse A stays sparse.  scs_select_batch
+ * then builds a sparse view instead of the n_b x m_pad dense one: bit for bit the two blocked
+ * copies scs_set_sparse would build from A[rows_b, :] (rows in batch order, a repeated row kept
+ * twice, the stored value type unchanged), y[rows_b] and a workspace of its own -- so a step on the
+ * view equals, bit for bit, the step of a context whose data is A[rows_b, :], y[rows_b].  ProxNSCORE
+ * and ProxGGNSCORE want dense tiles and keep the dense view; scs_method_init with a method of the
+ * other kind drops the views of the wrong kind.  A mode like scs_set_dense_f32: accepted at any
+ * time, forwarded to the devices of a multi-device context; changing it drops the pooled batch
+ * views (the registered list stays).  No effect on a dense A.
+ * Views are kept per batch, in the order built, while their bytes stay within a budget: the bytes
+ * the context's sparse data takes when scs_set_batches is called, or SCS_SPARSE_BATCH_CACHE_MB
+ * (read at scs_set_batches; 0 keeps nothing).  Batches beyond the budget share one refillable view
+ * per distinct size, rebuilt when it holds another batch.  A batch of more than 2^31 - 1 entries
+ * is refused with SCS_ERR_ARG at scs_select_batch.                                              */
+int scs_set_sparse_batches(scs_ctx* ctx, int on);
+/* The sparse batch views: how many are held, their device bytes, and the views built since
+ * scs_set_batches (a multi-device context: summed).  Any pointer may be NULL.                  */
+int scs_batch_info(scs_ctx* ctx, int64_t* nviews, int64_t* view_bytes, int64_t* builds);
 /* step!(method, model, reg_name, hμ, As, x, x_prev, ys, Cmat, iter;
  *       return_dx) (prox-N-SCORE.jl:34, prox-GGN-SCORE.jl:34,
  * prox-L-BFGS-SCORE.jl:69).  dx may be NULL.                               */

@@ -443,6 +443,20 @@ hipError_t csr_ingest(const void* rowptr, int ptr_bytes, const void* colidx, int
 hipError_t csr_claim(const int64_t* ptr, const int* idx, int64_t nrows, int64_t* cnt, uint32_t* rank, hipStream_t st);
 hipError_t csr_place(const int64_t* ptr, const int* idx, const void* val, int f32, int64_t nrows,
                      const int64_t* colptr, const uint32_t* rank, int* rowidx, void* valT, hipStream_t st);
+// A minibatch of a sparse A kept sparse (scs_set_sparse_batches).  Row side: blk_slice_size writes the
+// nblk·n + 1 segment sizes of rows[0..n) in the full blocked copy `ptr` (N rows; the last entry 0, for
+// blk_scan), blk_slice_copy moves the whole slots of those segments to the view's copy (dptr: the scanned
+// sizes).  Column side: csr_rows_size / csr_rows_gather copy the batch's plain CSR rows (n + 1 sizes,
+// then the entries at the scanned offsets optr).  launch_gather_y: yb[i] = y[rows[i]], zero from n to npad.
+hipError_t blk_slice_size(const int64_t* ptr, int64_t N, const int64_t* rows, int64_t n, int nblk, int64_t* cnt,
+                          hipStream_t st);
+hipError_t blk_slice_copy(const int64_t* sptr, const uint16_t* slidx, const void* sval, int f32, int64_t N,
+                          const int64_t* rows, int64_t n, int nblk, const int64_t* dptr, uint16_t* dlidx, void* dval,
+                          hipStream_t st);
+hipError_t csr_rows_size(const int64_t* rowptr, const int64_t* rows, int64_t n, int64_t* cnt, hipStream_t st);
+hipError_t csr_rows_gather(const int64_t* rowptr, const int* idx, const void* val, int f32, const int64_t* rows,
+                           int64_t n, const int64_t* optr, int* oidx, void* oval, hipStream_t st);
+hipError_t launch_gather_y(const double* y, const int64_t* rows, int64_t n, int64_t npad, double* yb, hipStream_t st);
 // sparse Gram G = Aᵀ diag(w) A (upper part, column j up to the end of its diagonal tile) from the
 // CSC copy and a Gram-blocked CSR copy (block width 2^shift, unpadded segments): Σ_r nnz_r² work
 int sparse_gram_shift();

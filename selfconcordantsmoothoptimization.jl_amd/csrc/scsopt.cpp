@@ -37,6 +37,7 @@
 #include "../../include/scsopt.h"
 #include "common.h"
 #include "kernels.h"
+#include "batch_plan.h"
 #include "shard_plan.h"
 
 using namespace scs;
@@ -62,6 +63,15 @@ struct DevBuf {
 // The N-dependent state of a context: the data rows with their sample-space workspace and the
 // GGN sample-space caches.  A minibatch (scs_set_batch) is a second view swapped in for the
 // duration of scs_step (the As, ys handed to step!, iterate.jl:205-207).
+// an LDS-blocked copy of a sparse A (sparse.hip)
+struct SpBlkT {
+  int shift = 0, nblk = 0;
+  int64_t nnz = 0;   // entries of the copy
+  int64_t* ptr = nullptr;
+  uint16_t* lidx = nullptr;
+  void* val = nullptr;
+};
+
 struct NView {
   double* A = nullptr;
   int a32 = 0;   // A holds float elements (scs_set_dense_f32): half the doubles allocated, widened on load
@@ -75,7 +85,13 @@ struct NView {
   int2* stiles = nullptr;
   int nstiles = 0;
   int64_t n1pad = 0;     // row stride of Ms: round_up(N + 1, 128) (lu.hip)
-  bool sparse = false;   // a batch view is always dense (Matrix(As'), iterate.jl:207)
+  bool sparse = false;   // a batch view is dense (Matrix(As'), iterate.jl:207) unless spv is set
+  // a sparse batch view (scs_set_sparse_batches): the batch's entry count and the two blocked copies
+  // scs_set_sparse would build from A[rows_b, :], exchanged with the context's by swap_view.  spv
+  // stays with the view object (it is not swapped).
+  bool spv = false;
+  int64_t nnz = 0;
+  SpBlkT bcsr, bcsc;
 };
 
 }  // namespace
@@ -119,13 +135,8 @@ struct scs_ctx {
   int64_t *rowptr = nullptr, *colptr = nullptr;
   int *colidx = nullptr, *rowidx = nullptr;
   void *val = nullptr, *valT = nullptr;
-  struct SpBlk {
-    int shift = 0, nblk = 0;
-    int64_t nnz = 0;   // entries of the copy
-    int64_t* ptr = nullptr;
-    uint16_t* lidx = nullptr;
-    void* val = nullptr;
-  } bcsr, bcsc;  // LDS-blocked copies used by the products (sparse.hip)
+  using SpBlk = SpBlkT;
+  SpBlk bcsr, bcsc;  // LDS-blocked copies used by the products (sparse.hip)
   SpBlk bgram;    // the sparse Gram's row copy: 2^sparse_gram_shift()-wide blocks, unpadded (built on first use)
   struct SegGram {   // the sparse Gram's variant-8 structure (build_gram_seg, on first use)
     int state = 0;   // 0 not tried, 1 built, -1 not built (memory / size): the Gram-blocked walk instead
@@ -311,6 +322,14 @@ struct scs_ctx {
   std::vector<NView> bpool;    // gathered views, one per distinct (local, global) batch size
   std::vector<int64_t> bheld;  // the batch each pool view currently holds (-1: none)
   int bview = -1;              // the selected batch's pool view (-1: the full data)
+  // scs_set_sparse_batches: under ProxLQNSCORE a sparse A's batches are sparse views (spool, one per
+  // plan slot: kept per batch within the budget, else one refillable slot per size; batch_plan.h).
+  // bscr: grow-only scratch of the view builds, freed with the list.
+  int sparse_batches = 0;
+  std::vector<NView> spool;
+  scs::BatchPlan bplan;
+  int spview = -1;             // the selected batch's sparse view (-1: none)
+  DevBuf bscr[20];
   int64_t bsel = -1;           // the selected batch (-1: the full data)
   // all ranks' rows of the full data or of the selected batch (GGN sample-space branch with
   // N_global + 1 <= m on several ranks)
@@ -950,6 +969,11 @@ void swap_view(scs_ctx* c, NView& v) {
   std::swap(c->stiles, v.stiles);
   std::swap(c->nstiles, v.nstiles);
   std::swap(c->n1pad, v.n1pad);
+  if (v.spv) {   // a sparse batch view: the products' blocked copies go with it (sp_f32 is the data's)
+    std::swap(c->nnz, v.nnz);
+    std::swap(c->bcsr, v.bcsr);
+    std::swap(c->bcsc, v.bcsc);
+  }
 }
 
 void free_view(scs_ctx* c, NView& v) {
@@ -958,6 +982,11 @@ void free_view(scs_ctx* c, NView& v) {
                      &v.Ms, &v.bS, &v.uN, &v.hvec, &v.hg})
     dfree_t(c, *p);
   dfree_t(c, v.stiles);
+  for (SpBlkT* B : {&v.bcsr, &v.bcsc}) {
+    dfree_t(c, B->ptr);
+    dfree_t(c, B->lidx);
+    dfree(c, B->val);
+  }
   v = NView();
 }
 
@@ -1006,20 +1035,37 @@ void free_test(scs_ctx* c) {
 // the call, swapped back even when the step fails
 struct BatchScope {
   scs_ctx* c;
-  int k;
-  explicit BatchScope(scs_ctx* cc) : c(cc), k(cc->bview) {
-    if (k >= 0) {
-      swap_view(c, c->bpool[k]);
-      invalidate_caches(c);
-    }
-  }
-  ~BatchScope() {
-    if (k >= 0) {
-      swap_view(c, c->bpool[k]);
-      invalidate_caches(c);
-    }
+  int k, ks;   // the dense pool view or the sparse view (at most one is >= 0)
+  explicit BatchScope(scs_ctx* cc) : c(cc), k(cc->bview), ks(cc->spview) { swap(); }
+  ~BatchScope() { swap(); }
+  void swap() {
+    if (k < 0 && ks < 0) return;
+    swap_view(c, ks >= 0 ? c->spool[ks] : c->bpool[k]);
+    invalidate_caches(c);
   }
 };
+
+void unselect_view(scs_ctx* c) { c->bview = c->spview = -1; }
+
+// the sparse views and the scratch of their builds (the registered list stays)
+void free_sparse_views(scs_ctx* c) {
+  for (NView& v : c->spool) free_view(c, v);
+  c->spool.clear();
+  c->bplan.slots.clear();
+  c->bplan.kept_bytes = 0;
+  c->spview = -1;
+  for (DevBuf& b : c->bscr) {
+    dfree(c, b.p);
+    b.bytes = 0;
+  }
+}
+
+void free_dense_views(scs_ctx* c) {
+  for (NView& v : c->bpool) free_view(c, v);
+  c->bpool.clear();
+  c->bheld.clear();
+  c->bview = -1;
+}
 
 void clear_batches(scs_ctx* c) {
   // the gathered rows of a batch index belong to the list they came from: a new list (a
@@ -1030,9 +1076,9 @@ void clear_batches(scs_ctx* c) {
     c->gview = NView();
     c->gview_ok = false;
   }
-  for (NView& v : c->bpool) free_view(c, v);
-  c->bpool.clear();
-  c->bheld.clear();
+  free_dense_views(c);
+  free_sparse_views(c);
+  c->bplan.reset(0);
   c->boff.clear();
   c->bglob.clear();
   c->bpos.clear();
@@ -1041,15 +1087,233 @@ void clear_batches(scs_ctx* c) {
   c->bsel = -1;
 }
 
+// ---- sparse batch views (scs_set_sparse_batches) ----------------------------------------
+size_t alloc_bytes(const scs_ctx* c, const void* p) {
+  if (p)
+    for (const DevBuf& a : c->allocs)
+      if (a.p == p) return a.bytes;
+  return 0;
+}
+
+// device bytes of a sparse view: y, the sample-space workspace and the two blocked copies
+int64_t sparse_view_bytes(const scs_ctx* c, const NView& v) {
+  size_t t = 0;
+  for (const void* p : {(const void*)v.y, (const void*)v.zpart, (const void*)v.z, (const void*)v.gN,
+                        (const void*)v.hN, (const void*)v.wN, (const void*)v.vN, (const void*)v.valpart,
+                        (const void*)v.tpart, (const void*)v.bcsr.ptr, (const void*)v.bcsr.lidx,
+                        (const void*)v.bcsr.val, (const void*)v.bcsc.ptr, (const void*)v.bcsc.lidx,
+                        (const void*)v.bcsc.val})
+    t += alloc_bytes(c, p);
+  return (int64_t)t;
+}
+
+// bytes the context's sparse data takes (the full data in place): the default budget of the kept views
+int64_t sparse_data_bytes(const scs_ctx* c) {
+  size_t t = 0;
+  for (const void* p : {(const void*)c->rowptr, (const void*)c->colptr, (const void*)c->colidx,
+                        (const void*)c->rowidx, (const void*)c->val, (const void*)c->valT,
+                        (const void*)c->bcsr.ptr, (const void*)c->bcsr.lidx, (const void*)c->bcsr.val,
+                        (const void*)c->bcsc.ptr, (const void*)c->bcsc.lidx, (const void*)c->bcsc.val})
+    t += alloc_bytes(c, p);
+  return (int64_t)t;
+}
+
+// scratch k of the view builds: at least n elements, contents undefined.  Grow-only while the batch
+// list lives, so a steady sequence of builds allocates nothing but the views' own arrays (§2d: the
+// stalls of a build are its hipMalloc calls).
+enum { BS_CNTR = 0, BS_PTRR, BS_RCNT, BS_RPTR, BS_IDX, BS_VAL, BS_CCNT, BS_RANK, BS_COLPTR, BS_ROWIDX, BS_VALT,
+       BS_ROWIDX_S, BS_VALT_S, BS_BCNT, BS_BFIRST, BS_PTRC, BS_TMP, BS_N };
+template <class T>
+T* bscratch(scs_ctx* c, int k, size_t n) {
+  static_assert(BS_N <= sizeof(c->bscr) / sizeof(c->bscr[0]), "scratch slots");
+  DevBuf& b = c->bscr[k];
+  const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
+  if (b.bytes < bytes) {
+    dfree(c, b.p);
+    b.bytes = 0;
+    b.p = dalloc<char>(c, bytes, false);
+    b.bytes = bytes;
+  }
+  return (T*)b.p;
+}
+
+// The sparse view of batch b: bit for bit the bcsr / bcsc that scs_set_sparse builds from
+// A[rows_b, :] (rows in batch order, batch positions as row numbers), y[rows_b] and a workspace of
+// its own.  Row side: a slice of the full row copy (sparse.hip blk_slice_*).  Column side: the
+// batch's CSR rows gathered, transposed as the device door transposes (csr_claim / csr_place),
+// sorted per column and blocked as build_blocked does -- on scratch, two read-backs of sizes.
+// Returns the view's slot in spool / bplan.
+int build_sparse_view(scs_ctx* c, int64_t b) {
+  const int64_t n = c->boff[b + 1] - c->boff[b], ng = c->bglob[b];
+  const int64_t* rows = c->brows + c->boff[b];
+  const int64_t N = c->N, m = c->m;
+  const int f32 = c->sp_f32;
+  const size_t vs = f32 ? sizeof(float) : sizeof(double);
+  const SpBlkT& F = c->bcsr;
+  NView v;
+  v.spv = true;
+  v.sparse = true;
+  v.N = n;
+  v.Nglob = ng;
+  // a rank that owns none of the batch's rows keeps one zero stage of workspace (N = 0, nnz = 0: the
+  // products launch nothing and its zero partials add nothing to the exchanged sums)
+  v.Npad = round_up(std::max<int64_t>(n, 1), 16);
+  v.nstage = v.Npad / 16;
+  SpBlkT R, Cc;
+  R.shift = F.shift;
+  R.nblk = F.nblk;
+  Cc.shift = spmv_blk_shift(n);
+  Cc.nblk = (int)std::max<int64_t>(ceil_div(n, int64_t(1) << Cc.shift), 1);
+  const int64_t nkR = (int64_t)R.nblk * n, nkC = (int64_t)Cc.nblk * m;
+  int64_t nnzpR = 0, nnzb = 0, nnzpC = 0;
+  int64_t *ptrR = nullptr, *ptrC = nullptr, *colptr_b = nullptr, *bfirst = nullptr;
+  int* rowidx_s = nullptr;
+  void* valT_s = nullptr;
+  auto scan = [&](const int64_t* cnt, int64_t* out, int64_t cntn) {
+    size_t tb = 0;
+    HCK(blk_scan(nullptr, &tb, cnt, out, cntn, c->st));
+    void* tmp = bscratch<char>(c, BS_TMP, tb);
+    HCK(blk_scan(tmp, &tb, cnt, out, cntn, c->st));
+  };
+  if (n > 0) {
+    int64_t* cntR = bscratch<int64_t>(c, BS_CNTR, nkR + 1);
+    ptrR = bscratch<int64_t>(c, BS_PTRR, nkR + 1);
+    int64_t* rcnt = bscratch<int64_t>(c, BS_RCNT, n + 1);
+    int64_t* rptr = bscratch<int64_t>(c, BS_RPTR, n + 1);
+    HCK(blk_slice_size(F.ptr, N, rows, n, R.nblk, cntR, c->st));
+    HCK(csr_rows_size(c->rowptr, rows, n, rcnt, c->st));
+    scan(cntR, ptrR, nkR + 1);
+    scan(rcnt, rptr, n + 1);
+    HCK(hipMemcpyAsync(&nnzpR, ptrR + nkR, sizeof(int64_t), hipMemcpyDeviceToHost, c->st));
+    HCK(hipMemcpyAsync(&nnzb, rptr + n, sizeof(int64_t), hipMemcpyDeviceToHost, c->st));
+    sync(c);
+    // the segmented sort counts its items in an int; the transposition's ranks are 32 bits wide
+    if (nnzb > (int64_t)INT32_MAX)
+      fail(c, SCS_ERR_ARG, "sparse batch %lld holds %lld entries (a sparse view takes at most 2^31 - 1)", (long long)b,
+           (long long)nnzb);
+    colptr_b = bscratch<int64_t>(c, BS_COLPTR, m + 1);
+    rowidx_s = bscratch<int>(c, BS_ROWIDX_S, nnzb);
+    valT_s = bscratch<char>(c, BS_VALT_S, (size_t)nnzb * vs);
+    if (nnzb > 0) {
+      int* idx_b = bscratch<int>(c, BS_IDX, nnzb);
+      void* val_b = bscratch<char>(c, BS_VAL, (size_t)nnzb * vs);
+      int64_t* ccnt = bscratch<int64_t>(c, BS_CCNT, m + 1);
+      uint32_t* rank = bscratch<uint32_t>(c, BS_RANK, nnzb);
+      int* rowidx_b = bscratch<int>(c, BS_ROWIDX, nnzb);
+      void* valT_b = bscratch<char>(c, BS_VALT, (size_t)nnzb * vs);
+      HCK(csr_rows_gather(c->rowptr, c->colidx, c->val, f32, rows, n, rptr, idx_b, val_b, c->st));
+      HCK(hipMemsetAsync(ccnt, 0, sizeof(int64_t) * (m + 1), c->st));
+      HCK(csr_claim(rptr, idx_b, n, ccnt, rank, c->st));
+      scan(ccnt, colptr_b, m + 1);
+      HCK(csr_place(rptr, idx_b, val_b, f32, n, colptr_b, rank, rowidx_b, valT_b, c->st));
+      int end_bit = 1;   // build_blocked's key width for n "columns" (the batch positions)
+      while ((int64_t(1) << end_bit) < n) ++end_bit;
+      size_t tb = 0;
+      HCK(sort_segments(nullptr, &tb, rowidx_b, rowidx_s, valT_b, valT_s, f32, nnzb, m, colptr_b, end_bit, c->st));
+      void* tmp = bscratch<char>(c, BS_TMP, tb);
+      HCK(sort_segments(tmp, &tb, rowidx_b, rowidx_s, valT_b, valT_s, f32, nnzb, m, colptr_b, end_bit, c->st));
+    } else {
+      HCK(hipMemsetAsync(colptr_b, 0, sizeof(int64_t) * (m + 1), c->st));
+    }
+    int64_t* bcnt = bscratch<int64_t>(c, BS_BCNT, nkC + 1);
+    bfirst = bscratch<int64_t>(c, BS_BFIRST, nkC + 1);
+    ptrC = bscratch<int64_t>(c, BS_PTRC, nkC + 1);
+    HCK(hipMemsetAsync(bcnt, 0, sizeof(int64_t) * (nkC + 1), c->st));
+    HCK(blk_count(colptr_b, rowidx_s, m, Cc.shift, bcnt, bfirst, c->st));
+    HCK(blk_pad(bcnt, nkC, f32, c->st));
+    scan(bcnt, ptrC, nkC + 1);
+    HCK(hipMemcpyAsync(&nnzpC, ptrC + nkC, sizeof(int64_t), hipMemcpyDeviceToHost, c->st));
+    sync(c);
+  }
+  // the view's bytes from its shapes (dalloc's sizes), to choose its slot before anything is allocated:
+  // a refillable slot gives its old view back first
+  const int nval = epilogue_blocks(v.Npad);
+  auto ab = [](int64_t cnt, size_t eb) { return (int64_t)(std::max<int64_t>(cnt, 1) * (int64_t)eb); };
+  const int64_t nR = n > 0 ? nkR + 1 : 1, nC = n > 0 ? nkC + 1 : 1;
+  const int64_t bytes = ab(v.Npad, 8) * 6 + ab((int64_t)R.nblk * v.Npad, 8) + ab(nval, 8) +
+                        ab((int64_t)Cc.nblk * c->mpad, 8) + ab(nR, 8) + ab(nC, 8) + ab(nnzpR + 8, 2) +
+                        ab(nnzpR + 8, vs) + ab(nnzpC + 8, 2) + ab(nnzpC + 8, vs);
+  const int old = c->bplan.refill_target(n, ng, bytes);
+  if (old >= 0) {
+    free_view(c, c->spool[old]);
+    c->bplan.slots[old].batch = -1;
+    c->bplan.slots[old].bytes = 0;
+  }
+  struct Guard {   // a failed build leaves no half-made view behind
+    scs_ctx* c;
+    NView* v;
+    SpBlkT *R, *Cc;
+    bool done = false;
+    ~Guard() {
+      if (done) return;
+      v->bcsr = *R;
+      v->bcsc = *Cc;
+      free_view(c, *v);
+    }
+  } guard{c, &v, &R, &Cc};
+  const int pad = spmv_pad_index();
+  R.ptr = dalloc<int64_t>(c, nR, n == 0);
+  R.lidx = dalloc<uint16_t>(c, nnzpR + 8, false);
+  R.val = f32 ? (void*)dalloc<float>(c, nnzpR + 8, false) : (void*)dalloc<double>(c, nnzpR + 8, false);
+  // the +8 tail reads as pad index / zero, as build_blocked leaves it
+  HCK(hipMemsetD16Async((hipDeviceptr_t)(R.lidx + nnzpR), (unsigned short)pad, 8, c->st));
+  HCK(hipMemsetAsync((char*)R.val + (size_t)nnzpR * vs, 0, 8 * vs, c->st));
+  Cc.ptr = dalloc<int64_t>(c, nC, n == 0);
+  Cc.lidx = dalloc<uint16_t>(c, nnzpC + 8, false);
+  HCK(hipMemsetD16Async((hipDeviceptr_t)Cc.lidx, (unsigned short)pad, (size_t)(nnzpC + 8), c->st));
+  Cc.val = f32 ? (void*)dalloc<float>(c, nnzpC + 8) : (void*)dalloc<double>(c, nnzpC + 8);
+  v.y = dalloc<double>(c, v.Npad, false);
+  HCK(launch_gather_y(c->y, rows, n, v.Npad, v.y, c->st));
+  if (n > 0) {
+    HCK(hipMemcpyAsync(R.ptr, ptrR, sizeof(int64_t) * nR, hipMemcpyDeviceToDevice, c->st));
+    HCK(hipMemcpyAsync(Cc.ptr, ptrC, sizeof(int64_t) * nC, hipMemcpyDeviceToDevice, c->st));
+    HCK(blk_slice_copy(F.ptr, F.lidx, F.val, f32, N, rows, n, R.nblk, R.ptr, R.lidx, R.val, c->st));
+    HCK(blk_scatter(colptr_b, rowidx_s, valT_s, f32, m, Cc.shift, Cc.ptr, bfirst, Cc.lidx, Cc.val, c->st));
+  }
+  v.nnz = nnzb;
+  v.bcsr = R;
+  v.bcsc = Cc;
+  R = Cc = SpBlkT();   // owned by v from here
+  swap_view(c, v);     // the workspace follows the view's nblk (nsplit / nchunk)
+  try {
+    alloc_nspace(c);
+  } catch (...) {
+    swap_view(c, v);
+    R = v.bcsr;
+    Cc = v.bcsc;
+    throw;
+  }
+  swap_view(c, v);
+  sync(c);
+  guard.done = true;
+  bool fresh = false;
+  const int k = c->bplan.place(b, n, ng, bytes, &fresh);
+  // the slot carries the bytes as allocated (they are `bytes` unless dalloc's sizes change)
+  const int64_t actual = sparse_view_bytes(c, v);
+  if (c->bplan.slots[k].kept) c->bplan.kept_bytes += actual - bytes;
+  c->bplan.slots[k].bytes = actual;
+  if (fresh) c->spool.push_back(v);
+  else c->spool[k] = v;
+  return k;
+}
+
 // select batch b (-1: the full data) for the following steps: its size's pool view is
 // allocated on first use (A / y rows + the sample-space workspace sized by its own Npad)
-// and re-gathered only when it holds another batch
+// and re-gathered only when it holds another batch.  With scs_set_sparse_batches on, a sparse A
+// under ProxLQNSCORE gets the batch's sparse view instead: kept per batch within the budget, else
+// rebuilt into the refillable slot of its size (batch_plan.h).
 void select_batch(scs_ctx* c, int64_t b) {
-  c->bview = -1;
+  unselect_view(c);
   c->bsel = b < 0 ? -1 : b;
   if (b < 0) return;
   // f(A, y, x) = 1/2 x'(A x) + y'x reads A as an m x m operator, not as samples
   if (c->loss == SCS_LOSS_QUADRATIC) fail(c, SCS_ERR_ARG, "the quadratic loss has no samples to batch");
+  if (c->sparse_batches && c->sparse && c->method_set && c->method == SCS_PROX_LQNSCORE) {
+    int ks = c->bplan.find(b);
+    if (ks < 0) ks = build_sparse_view(c, b);
+    c->spview = ks;
+    return;
+  }
   const int64_t n = c->boff[b + 1] - c->boff[b], ng = c->bglob[b];
   int k = -1;
   for (int i = 0; i < (int)c->bpool.size(); ++i)
@@ -3088,6 +3352,50 @@ int scs_set_dense_f32(scs_ctx* c, int on) {
   return guarded(c, [&] { c->dense_f32 = on ? 1 : 0; });
 }
 
+int scs_set_sparse_batches(scs_ctx* c, int on) {
+  if (is_group(c)) return group_run(c, [&](scs_ctx* s_, int) { return scs_set_sparse_batches(s_, on); });
+  return guarded(c, [&] {
+    const int v = on ? 1 : 0;
+    if (v == c->sparse_batches) return;
+    HCK(hipSetDevice(c->dev));
+    sync(c);
+    c->sparse_batches = v;
+    free_dense_views(c);   // the pooled views go, the registered list stays
+    free_sparse_views(c);
+    invalidate_caches(c);
+    if (c->bsel >= 0) select_batch(c, c->bsel);
+    sync(c);
+  });
+}
+
+int scs_batch_info(scs_ctx* c, int64_t* nviews, int64_t* view_bytes, int64_t* builds) {
+  if (is_group(c)) {   // the devices' figures summed
+    int64_t nv = 0, vb = 0, bd = 0;
+    for (scs_ctx* s_ : c->subs) {
+      int64_t a = 0, b = 0, d = 0;
+      const int rc = scs_batch_info(s_, &a, &b, &d);
+      if (rc != SCS_OK) {
+        c->err = s_->err;
+        return rc;
+      }
+      nv += a;
+      vb += b;
+      bd += d;
+    }
+    if (nviews) *nviews = nv;
+    if (view_bytes) *view_bytes = vb;
+    if (builds) *builds = bd;
+    return SCS_OK;
+  }
+  return guarded(c, [&] {
+    int64_t nv = 0;
+    for (const scs::BatchSlot& s_ : c->bplan.slots) nv += s_.batch >= 0 ? 1 : 0;
+    if (nviews) *nviews = nv;
+    if (view_bytes) *view_bytes = c->bplan.total_bytes();
+    if (builds) *builds = c->bplan.builds;
+  });
+}
+
 int scs_data_info(scs_ctx* c, int* a_elem_bytes, int64_t* a_bytes, int64_t* ctx_bytes) {
   if (is_group(c)) {   // device 0's element size, the devices' bytes summed
     int64_t ab = 0, cb = 0;
@@ -4000,6 +4308,18 @@ int scs_method_init(scs_ctx* c, int method, int ss_type, int use_prox, int mem) 
     c->lbfgs_pending = false;
     c->method_set = true;
     invalidate_caches(c);
+    // scs_set_sparse_batches: a pool view is sparse (ProxLQNSCORE) or dense (the Gram methods); views of
+    // the other kind go, and a selected batch gets its view of the right kind
+    if (c->sparse_batches && c->sparse) {
+      const bool sp = method == SCS_PROX_LQNSCORE;
+      const bool drop = sp ? !c->bpool.empty() : !c->spool.empty();
+      if (drop) {
+        sync(c);
+        if (sp) free_dense_views(c);
+        else free_sparse_views(c);
+        if (c->bsel >= 0) select_batch(c, c->bsel);
+      }
+    }
   });
 }
 
@@ -4070,6 +4390,9 @@ int scs_set_batches(scs_ctx* c, const int64_t* rows, const int64_t* offsets, int
     if (!loc.empty())
       HCK(hipMemcpyAsync(c->brows, loc.data(), sizeof(int64_t) * loc.size(), hipMemcpyHostToDevice, c->st));
     sync(c);
+    // the kept sparse views' budget: the bytes the sparse data takes now, or SCS_SPARSE_BATCH_CACHE_MB
+    c->bplan.reset(scs::batch_budget_bytes(std::getenv("SCS_SPARSE_BATCH_CACHE_MB"),
+                                           c->sparse ? sparse_data_bytes(c) : 0));
     // the exchange payload of the new list's sample-space batches (reduce_buffer_doubles)
     if (c->own_red && c->red && reduce_buffer_doubles(c) > c->red_cap) {
       dfree_t(c, c->red);
@@ -4311,7 +4634,7 @@ int scs_iterate_ex(scs_ctx* c, const double* x0, const double* x_star, int64_t m
     const int64_t iend = std::max<int64_t>(nb, 1);
     struct Unselect {
       scs_ctx* c;
-      ~Unselect() { c->bview = -1; }
+      ~Unselect() { unselect_view(c); }
     } unselect{c};
     double last_nx = 0.0, last_ndx = 0.0;
     // Device-resident loop (the full batch of a data loss): x, x_prev, x_new never leave the
@@ -4602,7 +4925,7 @@ int scs_iterate_ex(scs_ctx* c, const double* x0, const double* x_star, int64_t m
             step_newton(c, x, epoch, x_new, nullptr, &pri);
           dev_xn = xtag_of(c, x_new);   // the step's tail wrote x_new to c->xn (and downloaded it)
         }
-        c->bview = -1;
+        unselect_view(c);
         tend(c, T_STEP, e0);
         const double nx = nrm(x, nullptr);
         const double ndx = nrm(x_new, x);

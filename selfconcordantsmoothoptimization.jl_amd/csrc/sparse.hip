@@ -326,7 +326,7 @@ const char* spmv_kernel_name(int f32) {
 hipError_t launch_spmv_blk(const int64_t* ptr, const uint16_t* lidx, const void* val, int f32, const double* x,
                            int64_t nrows, int64_t ncols, int shift, int64_t nnz, double* out, int64_t ldo,
                            hipStream_t st) {
-  if (nrows <= 0) return hipSuccess;
+  if (nrows <= 0 || ncols <= 0) return hipSuccess;   // no rows, or no block to gather from (an empty view)
   const int nblk = (int)ceil_div(ncols, (int64_t)1 << shift);
   // one 1024-row chunk per workgroup; fp64 in 4-entry slots, fp32 in 8-entry slots
   const dim3 grid((unsigned)ceil_div(nrows, SPB_ROWS), (unsigned)nblk);
@@ -575,6 +575,172 @@ hipError_t csr_place(const int64_t* ptr, const int* idx, const void* val, int f3
   else
     hipLaunchKernelGGL(csr_place_kernel<double>, grid, dim3(256), 0, st, ptr, idx, (const double*)val, nrows, colptr,
                        rank, rowidx, (double*)valT);
+  return hipGetLastError();
+}
+
+// ---- a minibatch of a sparse A as a sparse view (scs_set_sparse_batches) ---------------------------
+// The view holds the blocked copies that scs_set_sparse would build from A[rows, :].
+//
+// Row side: the batch's row copy is a slice of the full data's.  Segment (block b, batch row i) is
+// ptr[b·N + rows[i]] .. ptr[b·N + rows[i] + 1] of the full copy: already sorted, already padded to
+// whole slots with the pad index (a repeated row is copied twice).  blk_slice_size writes the
+// nblk·n segment sizes (and a closing 0), blk_scan turns them into the view's ptr, and
+// blk_slice_copy moves the slots: a wave owns 64 batch rows of one block, whose destination is one
+// contiguous slot range; it walks that range 64 slots a trip, every lane busy -- the lane finds the
+// row of its slot by bisection over the wave's 64 row starts (lane k holds row k's) and reads the
+// slot from that row's source segment.  A slot is the granule win_load reads: fp64 32 B of values +
+// 8 B of indices, fp32 32 B of values + 16 B of indices, moved with 16-byte accesses.  Positions are
+// 64-bit; a wave's own range is counted in 32 bits (64 segments of at most 2^14 entries).
+__global__ void blk_slice_size_kernel(const int64_t* __restrict__ ptr, int64_t N, const int64_t* __restrict__ rows,
+                                      int64_t n, int nblk, int64_t* __restrict__ cnt) {
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t nk = (int64_t)nblk * n;
+  if (k > nk) return;
+  if (k == nk) {
+    cnt[k] = 0;
+    return;
+  }
+  const int64_t b = k / n, i = k - b * n;
+  const int64_t s = b * N + rows[i];
+  cnt[k] = ptr[s + 1] - ptr[s];
+}
+
+template <typename VT, int SLOT>
+__global__ __launch_bounds__(256) void blk_slice_copy_kernel(const int64_t* __restrict__ sptr,
+                                                             const uint16_t* __restrict__ slidx,
+                                                             const VT* __restrict__ sval, int64_t N,
+                                                             const int64_t* __restrict__ rows, int64_t n,
+                                                             const int64_t* __restrict__ dptr,
+                                                             uint16_t* __restrict__ dlidx, VT* __restrict__ dval) {
+  constexpr int SH = SLOT == 4 ? 2 : 3;
+  constexpr int VPS = SLOT * (int)sizeof(VT) / 16;   // 16-byte value accesses per slot (2)
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.y;
+  const int64_t rw0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64;
+  if (rw0 >= n) return;
+  const int nrw = (int)min((int64_t)64, n - rw0);
+  const int64_t* dp = dptr + (int64_t)b * n + rw0;
+  const int64_t db = dp[0] >> SH;                      // the wave's first destination slot
+  const int total = (int)((dp[nrw] >> SH) - db);       // its slot count
+  // lane k: destination start of row k relative to db (lanes past nrw: total), source start slot
+  const int st = lane < nrw ? (int)((dp[lane] >> SH) - db) : total;
+  const int64_t ss = lane < nrw ? (sptr[(int64_t)b * N + rows[rw0 + lane]] >> SH) : 0;
+  for (int base = 0; base < total; base += 64) {
+    const int j = base + lane;
+    // r = the last row with st_r <= j (empty rows share a start with their successor: skipped)
+    int lo = 0, hi = 63;
+    for (int it = 0; it < 6; ++it) {
+      const int mid = (lo + hi + 1) >> 1;
+      const int sm = __shfl(st, mid, 64);   // every lane takes part
+      if (sm <= j) lo = mid;
+      else hi = mid - 1;
+    }
+    const int sr = __shfl(st, lo, 64);
+    const long long so = __shfl((long long)ss, lo, 64);
+    if (j < total) {
+      const int64_t s = (int64_t)so + (j - sr), d = db + j;
+      typedef unsigned int v4u __attribute__((ext_vector_type(4)));
+      const v4u* vs = (const v4u*)(sval + SLOT * s);
+      v4u* vd = (v4u*)(dval + SLOT * d);
+      v4u t[VPS];
+#pragma unroll
+      for (int q = 0; q < VPS; ++q) t[q] = vs[q];
+      if (SLOT == 4) {
+        const uint64_t ix = *(const uint64_t*)(slidx + 4 * s);
+#pragma unroll
+        for (int q = 0; q < VPS; ++q) vd[q] = t[q];
+        *(uint64_t*)(dlidx + 4 * d) = ix;
+      } else {
+        const v4u ix = *(const v4u*)(slidx + 8 * s);
+#pragma unroll
+        for (int q = 0; q < VPS; ++q) vd[q] = t[q];
+        *(v4u*)(dlidx + 8 * d) = ix;
+      }
+    }
+  }
+}
+
+hipError_t blk_slice_size(const int64_t* ptr, int64_t N, const int64_t* rows, int64_t n, int nblk, int64_t* cnt,
+                          hipStream_t st) {
+  const int64_t nk = (int64_t)nblk * n + 1;
+  hipLaunchKernelGGL(blk_slice_size_kernel, dim3((unsigned)ceil_div(nk, 256)), dim3(256), 0, st, ptr, N, rows, n, nblk,
+                     cnt);
+  return hipGetLastError();
+}
+
+hipError_t blk_slice_copy(const int64_t* sptr, const uint16_t* slidx, const void* sval, int f32, int64_t N,
+                          const int64_t* rows, int64_t n, int nblk, const int64_t* dptr, uint16_t* dlidx, void* dval,
+                          hipStream_t st) {
+  if (n <= 0 || nblk <= 0) return hipSuccess;
+  const dim3 grid((unsigned)ceil_div(n, 256), (unsigned)nblk);   // 4 waves of 64 rows per workgroup
+  if (f32)
+    hipLaunchKernelGGL((blk_slice_copy_kernel<float, 8>), grid, dim3(256), 0, st, sptr, slidx, (const float*)sval, N,
+                       rows, n, dptr, dlidx, (float*)dval);
+  else
+    hipLaunchKernelGGL((blk_slice_copy_kernel<double, 4>), grid, dim3(256), 0, st, sptr, slidx, (const double*)sval,
+                       N, rows, n, dptr, dlidx, (double*)dval);
+  return hipGetLastError();
+}
+
+// Column side, step 1: the batch's plain CSR rows (sorted by column, as the full copy holds them)
+// gathered into temporaries -- sizes (a closing 0 for the scan), then one wave per batch row.  The
+// transposition (csr_claim / csr_place with batch positions as row numbers), the per-column sort
+// and the blocked build then run on the temporaries as they do on the full data.
+__global__ void csr_rows_size_kernel(const int64_t* __restrict__ rowptr, const int64_t* __restrict__ rows, int64_t n,
+                                     int64_t* __restrict__ cnt) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > n) return;
+  if (i == n) {
+    cnt[i] = 0;
+    return;
+  }
+  const int64_t r = rows[i];
+  cnt[i] = rowptr[r + 1] - rowptr[r];
+}
+
+template <typename VT>
+__global__ void csr_rows_gather_kernel(const int64_t* __restrict__ rowptr, const int* __restrict__ idx,
+                                       const VT* __restrict__ val, const int64_t* __restrict__ rows, int64_t n,
+                                       const int64_t* __restrict__ optr, int* __restrict__ oidx,
+                                       VT* __restrict__ oval) {
+  const int lane = threadIdx.x & 63;
+  const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= n) return;
+  const int64_t r = rows[i];
+  const int64_t p0 = rowptr[r], len = rowptr[r + 1] - p0, d0 = optr[i];
+  for (int64_t q = lane; q < len; q += 64) {
+    oidx[d0 + q] = idx[p0 + q];
+    oval[d0 + q] = val[p0 + q];
+  }
+}
+
+__global__ void gather_y_kernel(const double* __restrict__ y, const int64_t* __restrict__ rows, int64_t n,
+                                int64_t npad, double* __restrict__ yb) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < npad) yb[i] = i < n ? y[rows[i]] : 0.0;
+}
+
+hipError_t csr_rows_size(const int64_t* rowptr, const int64_t* rows, int64_t n, int64_t* cnt, hipStream_t st) {
+  hipLaunchKernelGGL(csr_rows_size_kernel, dim3((unsigned)ceil_div(n + 1, 256)), dim3(256), 0, st, rowptr, rows, n,
+                     cnt);
+  return hipGetLastError();
+}
+
+hipError_t csr_rows_gather(const int64_t* rowptr, const int* idx, const void* val, int f32, const int64_t* rows,
+                           int64_t n, const int64_t* optr, int* oidx, void* oval, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  const dim3 grid((unsigned)ceil_div(n, 4));
+  if (f32)
+    hipLaunchKernelGGL(csr_rows_gather_kernel<float>, grid, dim3(256), 0, st, rowptr, idx, (const float*)val, rows, n,
+                       optr, oidx, (float*)oval);
+  else
+    hipLaunchKernelGGL(csr_rows_gather_kernel<double>, grid, dim3(256), 0, st, rowptr, idx, (const double*)val, rows,
+                       n, optr, oidx, (double*)oval);
+  return hipGetLastError();
+}
+
+hipError_t launch_gather_y(const double* y, const int64_t* rows, int64_t n, int64_t npad, double* yb, hipStream_t st) {
+  hipLaunchKernelGGL(gather_y_kernel, dim3((unsigned)ceil_div(npad, 256)), dim3(256), 0, st, y, rows, n, npad, yb);
   return hipGetLastError();
 }
 

@@ -15,7 +15,8 @@ using SelfConcordantSmoothOptimization
 import SelfConcordantSmoothOptimization: step!, init!, ProximalMethod, ProxModel, is_interval_set
 
 export DeviceProblem, configure!, iterate_device!, set_gram_cache!, set_solver!, rccl_unique_id, set_comm_rccl!,
-       set_comm_callback!, set_test!, set_test_device!, set_compute_f32!, fallback_counts, data_info, samplewise
+       set_comm_callback!, set_test!, set_test_device!, set_compute_f32!, fallback_counts, data_info, samplewise,
+       set_sparse_batches!, batch_info
 
 const lib = joinpath(@__DIR__, "..", "scsopt", "libscsopt.so")
 
@@ -329,8 +330,10 @@ function DeviceProblem(A::SparseMatrixCSC{Float64}, y::AbstractVector, x0::Vecto
                        out_fn::Union{Symbol,Nothing}=nothing, scale::Float64=1.0 / size(A, 1),
                        L=nothing, sol::Vector{Float64}=zero(x0), C_set=nothing, P=nothing, device::Integer=0,
                        val_f32::Bool=false, N_global::Integer=size(A, 1), row0::Integer=0, Atest=nothing,
-                       ytest=nothing, Ntest_global::Integer=0, test_row0::Integer=0)
+                       ytest=nothing, Ntest_global::Integer=0, test_row0::Integer=0,
+                       sparse_batches::Bool=false)
     ctx = create_ctx(device)
+    sparse_batches && chk(ccall((:scs_set_sparse_batches, lib), Cint, (Ptr{Cvoid}, Cint), ctx, 1), ctx)
     N, m = size(A)
     yv = Vector{Float64}(y)
     At = SparseMatrixCSC(transpose(A))
@@ -390,6 +393,21 @@ function set_test_sparse_device!(model::DeviceProblem, rowptr::Ptr{Cvoid}, colid
               model.ctx, Ntest, nnz, rowptr, pb, colidx, ib, val, vb, val_f32 ? 1 : 0, yp, stream, Ntest_global,
               test_row0), model.ctx)
     return model
+end
+
+# Minibatches of a sparse A stay sparse under ProxLQNSCORE (scs_set_sparse_batches; off by default:
+# the batch is then the reference's Matrix(As')).  Changing the mode drops the pooled batch views.
+function set_sparse_batches!(model::DeviceProblem, on::Bool=true)
+    chk(ccall((:scs_set_sparse_batches, lib), Cint, (Ptr{Cvoid}, Cint), model.ctx, on ? 1 : 0), model.ctx)
+    return model
+end
+
+# (sparse batch views held, their device bytes, views built since the batch list was registered)
+function batch_info(model::DeviceProblem)
+    nv = Ref{Int64}(0); vb = Ref{Int64}(0); bd = Ref{Int64}(0)
+    chk(ccall((:scs_batch_info, lib), Cint, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}), model.ctx, nv, vb, bd),
+        model.ctx)
+    return nv[], vb[], bd[]
 end
 
 # the device's CSC copy of a sparse A, back on the host as a SparseMatrixCSC (values widened)

@@ -162,6 +162,8 @@ _SIGS = {
     "scs_set_group_map": (C.c_int, [C.c_void_p, c_i64p, C.c_int64]),
     "scs_set_batches": (C.c_int, [C.c_void_p, c_i64p, c_i64p, C.c_int64]),
     "scs_select_batch": (C.c_int, [C.c_void_p, C.c_int64]),
+    "scs_set_sparse_batches": (C.c_int, [C.c_void_p, C.c_int]),
+    "scs_batch_info": (C.c_int, [C.c_void_p, c_i64p, c_i64p, c_i64p]),
     "scs_step": (C.c_int, [C.c_void_p, c_dp, c_dp, C.c_int64, c_dp, c_dp, c_dp]),
     "scs_step_grad": (C.c_int, [C.c_void_p, c_dp, c_dp, C.c_int64, c_dp, c_dp, c_dp, c_dp]),
     "scs_iterate": (C.c_int, [C.c_void_p, c_dp, c_dp, C.c_int64, C.c_double, C.c_double, C.c_int, c_dp,

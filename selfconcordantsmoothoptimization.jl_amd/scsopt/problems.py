@@ -96,7 +96,7 @@ class Problem:
     def __init__(self, *args, Atest=None, ytest=None, L=None, sol=None, C_set=None, P=None,
                  out_fn: Optional[OutFn] = None, name=None, device=0, comm=None, N_global=None, row0=0,
                  sparse_f32=False, devices=None, device_exchange="rccl", Ntest_global=None, test_row0=0,
-                 dense_f32=False, _ctx=None):
+                 dense_f32=False, sparse_batches=False, _ctx=None):
         if len(args) == 5:
             A, y, x0, f, lam = args
         elif len(args) == 3:
@@ -136,6 +136,8 @@ class Problem:
         # dense_f32: a dense A (and dense held-out rows) stored as fp32 on the device, fp64 arithmetic --
         # bit for bit what the same values widened to fp64 give (scs_set_dense_f32)
         self.dense_f32 = bool(dense_f32)
+        if sparse_batches:   # a mode of the context: set before any batch view exists
+            self.ctx.check(_lib.lib.scs_set_sparse_batches(self.ctx.h, 1))
         if comm is not None and comm.active and _ctx is None:
             comm.attach(self.ctx)
         if _ctx is None:
@@ -718,6 +720,20 @@ class Problem:
                                                 off.ctypes.data_as(_lib.c_i64p), len(rs)))
         if self.comm is not None and self.comm.active:   # the exchange payload may have grown
             self.comm.bind_buffer(self.ctx)
+
+    def set_sparse_batches(self, on=True):
+        """Opt-in: under ProxLQNSCORE a minibatch of a sparse A stays sparse -- scs_select_batch builds
+        the blocked copies scs_set_sparse would build from A[rows_b, :] instead of the n_b x m_pad dense
+        view, bit for bit, and keeps them per batch within a budget (the bytes of the sparse data, or
+        SCS_SPARSE_BATCH_CACHE_MB).  ProxNSCORE / ProxGGNSCORE keep the dense view.  Changing the mode
+        drops the pooled views; the registered list stays.  scs_set_sparse_batches."""
+        self.ctx.check(_lib.lib.scs_set_sparse_batches(self.ctx.h, int(bool(on))))
+
+    def batch_info(self):
+        """(sparse batch views held, their device bytes, views built since set_batches) -- scs_batch_info."""
+        nv, vb, bd = C.c_int64(), C.c_int64(), C.c_int64()
+        self.ctx.check(_lib.lib.scs_batch_info(self.ctx.h, C.byref(nv), C.byref(vb), C.byref(bd)))
+        return int(nv.value), int(vb.value), int(bd.value)
 
     def select_batch(self, b=-1):
         """The registered batch the following step! calls see as As, ys (-1: the full data)."""
