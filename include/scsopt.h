@@ -486,6 +486,21 @@ int scs_select_batch(scs_ctx* ctx, int64_t b);
  * per distinct size, rebuilt when it holds another batch.  A batch of more than 2^31 - 1 entries
  * is refused with SCS_ERR_ARG at scs_select_batch.                                              */
 int scs_set_sparse_batches(scs_ctx* ctx, int on);
+/* Opt-in (default 0): ProxGGNSCORE's sample-space branch (N + 1 <= m, prox-GGN-SCORE.jl:124-127) on a
+ * sparse A forms P = A diag(1/Hr) Aᵀ from the nonzeros (sum_j cnt_j^2 multiply-adds over the columns'
+ * entry counts) instead of a dense mirror of A, a dense Aᵀ copy and MFMA tiles.  P(k, i), k <= i, is
+ * the sum over row i's entries in stored order of (h_j a_ij) a_kj; SCS_SPARSE_SAMPLE_KERNEL (0 plain
+ * walk, the default; 1 packed walk) and SCS_SPARSE_GRAM_SHIFT change the kernel, not a bit of P.  The (N+1)^2
+ * system, its LU or QR and the rest of the step are unchanged.  With scs_set_sparse_batches also on,
+ * a batch with n_b + 1 <= m gets a sparse view under ProxGGNSCORE too (the pieces of a ProxLQNSCORE
+ * view, the batch's CSR and a blocked copy of its CSC), so a step on it equals, bit for bit, the
+ * step of a context holding A[rows_b, :], y[rows_b] with this mode on; the system scratch (2 n_b^2
+ * doubles) is kept once per distinct batch size, not per view.  Batches with n_b + 1 > m and
+ * ProxNSCORE keep the dense view.  A mode like scs_set_sparse_batches: accepted at any time,
+ * forwarded to the devices of a multi-device context, changing it drops the pooled views.  It is
+ * stored and has NO effect on a sharded or multi-device context (the sample-space branch across
+ * ranks needs a dense A) and on a dense A.                                                      */
+int scs_set_sparse_sample(scs_ctx* ctx, int on);
 /* The sparse batch views: how many are held, their device bytes, and the views built since
  * scs_set_batches (a multi-device context: summed).  Any pointer may be NULL.                  */
 int scs_batch_info(scs_ctx* ctx, int64_t* nviews, int64_t* view_bytes, int64_t* builds);
@@ -552,6 +567,10 @@ int scs_prox_eval(scs_ctx* ctx, const double* z, const double* Hr, double lam,
                   double alpha, double* out);
 /* G = Aᵀ diag(w) A (local rows; lower triangle + diagonal tiles), ldg >= m. */
 int scs_gram_eval(scs_ctx* ctx, const double* w, double* G, int64_t ldg);
+/* P = A diag(h) Aᵀ (h: m weights) of the selected batch or the full data, formed the way a
+ * ProxGGNSCORE sample-space step forms it (from the nonzeros with scs_set_sparse_sample on a sparse
+ * A, else Aᵀ copy + tiles), symmetrized; N x N into P, ldp >= N.  One rank.                     */
+int scs_sample_gram_eval(scs_ctx* ctx, const double* h, double* P, int64_t ldp);
 /* out = Aᵀ v (local rows)                                                  */
 int scs_gemv_t_eval(scs_ctx* ctx, const double* v, double* out);
 /* out = A x (local rows)                                                   */

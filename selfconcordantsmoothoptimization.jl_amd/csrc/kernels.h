@@ -480,6 +480,16 @@ const char* sparse_gram_kernel_name(int f32, int64_t entries);
 hipError_t launch_sparse_gram(const int64_t* colptr, const int* rowidx, const void* valT, const int64_t* bptr,
                               const uint16_t* lidx, const void* bval, int64_t entries, int f32, const double* w,
                               int64_t nrows, int64_t m, int shift, double* G, int64_t ldg, hipStream_t st);
+// P = A diag(h) Aᵀ of a sparse A from its nonzeros (scs_set_sparse_sample): the CSR of A (n x m) and
+// the Gram-blocked copy of its CSC (2^shift-wide blocks of rows); the upper triangle, element
+// (k <= i, i) at P[i·ldp + k] up to the end of i's 128-row diagonal tile.  SCS_SPARSE_SAMPLE_KERNEL:
+// 0 the plain arm (launch_sparse_gram's walks, roles exchanged), 1 the packed walk -- the same bits.
+int sparse_sample_kernel();
+const char* sparse_sample_kernel_name(int f32, int64_t entries);
+hipError_t launch_sparse_sample_gram(const int64_t* rowptr, const int* colidx, const void* val, const int64_t* bptr,
+                                     const uint16_t* lidx, const void* bval, int64_t entries, int f32,
+                                     const double* h, int64_t n, int64_t m, int shift, double* P, int64_t ldp,
+                                     hipStream_t st);
 size_t sparse_layer_map_bytes(int k);
 void sparse_layer_maps(uint64_t seed, int k, int64_t N, void* out_host);
 hipError_t launch_gen_sparse(int64_t N, int64_t m, int k, uint64_t seed, const void* Ldev, int f32, double scale,

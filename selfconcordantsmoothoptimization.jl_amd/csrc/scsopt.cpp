@@ -92,6 +92,21 @@ struct NView {
   bool spv = false;
   int64_t nnz = 0;
   SpBlkT bcsr, bcsc;
+  // ... which also serves ProxGGNSCORE's sample-space branch (scs_set_sparse_sample, ssv): the batch's
+  // plain CSR and the Gram-blocked copy of its CSC, exchanged with the context's rowptr / colidx / val
+  // and sgram.  The (n+1)² system scratch is not the view's: sample_sys keeps one set per size.
+  bool ssv = false;
+  int64_t* rowptr = nullptr;
+  int* colidx = nullptr;
+  void* val = nullptr;
+  SpBlkT sgram;
+};
+
+// the per-step scratch of the sparse sample-space branch for n samples: P, the (n+1)² system and its
+// vectors (2·n² doubles), shared by the full data or every batch view of that size
+struct SampleSys {
+  int64_t N = -1, NpS = 0, n1pad = 0;
+  double *Ps = nullptr, *Ms = nullptr, *bS = nullptr, *uN = nullptr, *hvec = nullptr, *hg = nullptr;
 };
 
 }  // namespace
@@ -138,6 +153,12 @@ struct scs_ctx {
   using SpBlk = SpBlkT;
   SpBlk bcsr, bcsc;  // LDS-blocked copies used by the products (sparse.hip)
   SpBlk bgram;    // the sparse Gram's row copy: 2^sparse_gram_shift()-wide blocks, unpadded (built on first use)
+  // scs_set_sparse_sample: ProxGGNSCORE's sample-space P = A diag(h) Aᵀ of a sparse A from its nonzeros.
+  // sgram: the Gram-blocked copy of the CSC (columns cut into 2^sparse_gram_shift()-wide blocks of
+  // rows, unpadded; built on first use, a batch view brings its own); ssys: the system scratch per size
+  int sparse_sample = 0;
+  SpBlk sgram;
+  std::vector<SampleSys> ssys;
   struct SegGram {   // the sparse Gram's variant-8 structure (build_gram_seg, on first use)
     int state = 0;   // 0 not tried, 1 built, -1 not built (memory / size): the Gram-blocked walk instead
     int shift = 0;
@@ -327,6 +348,8 @@ struct scs_ctx {
   // bscr: grow-only scratch of the view builds, freed with the list.
   int sparse_batches = 0;
   std::vector<NView> spool;
+  int spool_kind = 1;          // what spool's views serve: 1 ProxLQNSCORE, 2 ProxGGNSCORE's sample space too
+  int vkind = 0;               // the kind of view the method set last asks for (batch_view_kind)
   scs::BatchPlan bplan;
   int spview = -1;             // the selected batch's sparse view (-1: none)
   DevBuf bscr[20];
@@ -974,6 +997,12 @@ void swap_view(scs_ctx* c, NView& v) {
     std::swap(c->bcsr, v.bcsr);
     std::swap(c->bcsc, v.bcsc);
   }
+  if (v.ssv) {
+    std::swap(c->rowptr, v.rowptr);
+    std::swap(c->colidx, v.colidx);
+    std::swap(c->val, v.val);
+    std::swap(c->sgram, v.sgram);
+  }
 }
 
 void free_view(scs_ctx* c, NView& v) {
@@ -982,12 +1011,30 @@ void free_view(scs_ctx* c, NView& v) {
                      &v.Ms, &v.bS, &v.uN, &v.hvec, &v.hg})
     dfree_t(c, *p);
   dfree_t(c, v.stiles);
-  for (SpBlkT* B : {&v.bcsr, &v.bcsc}) {
+  for (SpBlkT* B : {&v.bcsr, &v.bcsc, &v.sgram}) {
     dfree_t(c, B->ptr);
     dfree_t(c, B->lidx);
     dfree(c, B->val);
   }
+  dfree_t(c, v.rowptr);
+  dfree_t(c, v.colidx);
+  dfree(c, v.val);
   v = NView();
+}
+
+void free_sample_sys(scs_ctx* c) {
+  for (SampleSys& S : c->ssys)
+    for (double** p : {&S.Ps, &S.Ms, &S.bS, &S.uN, &S.hvec, &S.hg}) dfree_t(c, *p);
+  c->ssys.clear();
+}
+
+// 0: dense batch views, 1: sparse views for ProxLQNSCORE, 2: sparse views for ProxGGNSCORE's batches
+// with n_b + 1 <= m (dense ones for the rest) -- one rank only: the sharded sample branch needs a dense A
+int batch_view_kind(const scs_ctx* c, int method) {
+  if (!c->sparse_batches || !c->sparse) return 0;
+  if (method == SCS_PROX_LQNSCORE) return 1;
+  if (method == SCS_PROX_GGNSCORE && c->sparse_sample && !sharded(c)) return 2;
+  return 0;
 }
 
 // the held-out view <-> the context's data fields (f's fields only: rows, y, the products'
@@ -1078,6 +1125,7 @@ void clear_batches(scs_ctx* c) {
   }
   free_dense_views(c);
   free_sparse_views(c);
+  free_sample_sys(c);
   c->bplan.reset(0);
   c->boff.clear();
   c->bglob.clear();
@@ -1095,14 +1143,16 @@ size_t alloc_bytes(const scs_ctx* c, const void* p) {
   return 0;
 }
 
-// device bytes of a sparse view: y, the sample-space workspace and the two blocked copies
+// device bytes of a sparse view: y, the sample-space workspace and the two blocked copies (a view for
+// the GGN sample space: also its plain CSR and the Gram-blocked column copy)
 int64_t sparse_view_bytes(const scs_ctx* c, const NView& v) {
   size_t t = 0;
   for (const void* p : {(const void*)v.y, (const void*)v.zpart, (const void*)v.z, (const void*)v.gN,
                         (const void*)v.hN, (const void*)v.wN, (const void*)v.vN, (const void*)v.valpart,
                         (const void*)v.tpart, (const void*)v.bcsr.ptr, (const void*)v.bcsr.lidx,
                         (const void*)v.bcsr.val, (const void*)v.bcsc.ptr, (const void*)v.bcsc.lidx,
-                        (const void*)v.bcsc.val})
+                        (const void*)v.bcsc.val, (const void*)v.rowptr, (const void*)v.colidx, (const void*)v.val,
+                        (const void*)v.sgram.ptr, (const void*)v.sgram.lidx, (const void*)v.sgram.val})
     t += alloc_bytes(c, p);
   return (int64_t)t;
 }
@@ -1122,7 +1172,7 @@ int64_t sparse_data_bytes(const scs_ctx* c) {
 // list lives, so a steady sequence of builds allocates nothing but the views' own arrays (§2d: the
 // stalls of a build are its hipMalloc calls).
 enum { BS_CNTR = 0, BS_PTRR, BS_RCNT, BS_RPTR, BS_IDX, BS_VAL, BS_CCNT, BS_RANK, BS_COLPTR, BS_ROWIDX, BS_VALT,
-       BS_ROWIDX_S, BS_VALT_S, BS_BCNT, BS_BFIRST, BS_PTRC, BS_TMP, BS_N };
+       BS_ROWIDX_S, BS_VALT_S, BS_BCNT, BS_BFIRST, BS_PTRC, BS_TMP, BS_GCNT, BS_GFIRST, BS_GPTR, BS_N };
 template <class T>
 T* bscratch(scs_ctx* c, int k, size_t n) {
   static_assert(BS_N <= sizeof(c->bscr) / sizeof(c->bscr[0]), "scratch slots");
@@ -1142,8 +1192,11 @@ T* bscratch(scs_ctx* c, int k, size_t n) {
 // its own.  Row side: a slice of the full row copy (sparse.hip blk_slice_*).  Column side: the
 // batch's CSR rows gathered, transposed as the device door transposes (csr_claim / csr_place),
 // sorted per column and blocked as build_blocked does -- on scratch, two read-backs of sizes.
+// ssv (ProxGGNSCORE's sample space, scs_set_sparse_sample): the view also keeps the gathered CSR rows and
+// the Gram-blocked copy of its CSC -- colptr_b / rowidx_s / valT_s cut into 2^sparse_gram_shift()-wide
+// blocks of batch positions, unpadded, as build_gram_blocked cuts the rows.
 // Returns the view's slot in spool / bplan.
-int build_sparse_view(scs_ctx* c, int64_t b) {
+int build_sparse_view(scs_ctx* c, int64_t b, bool ssv) {
   const int64_t n = c->boff[b + 1] - c->boff[b], ng = c->bglob[b];
   const int64_t* rows = c->brows + c->boff[b];
   const int64_t N = c->N, m = c->m;
@@ -1152,6 +1205,7 @@ int build_sparse_view(scs_ctx* c, int64_t b) {
   const SpBlkT& F = c->bcsr;
   NView v;
   v.spv = true;
+  v.ssv = ssv;
   v.sparse = true;
   v.N = n;
   v.Nglob = ng;
@@ -1169,6 +1223,13 @@ int build_sparse_view(scs_ctx* c, int64_t b) {
   int64_t *ptrR = nullptr, *ptrC = nullptr, *colptr_b = nullptr, *bfirst = nullptr;
   int* rowidx_s = nullptr;
   void* valT_s = nullptr;
+  SpBlkT& Gb = v.sgram;   // (ssv) owned by v from the start: free_view gives a failed build's arrays back
+  Gb.shift = sparse_gram_shift();
+  Gb.nblk = (int)std::max<int64_t>(ceil_div(n, int64_t(1) << Gb.shift), 1);
+  const int64_t nkG = (int64_t)Gb.nblk * m;
+  int64_t *rptr_s = nullptr, *gfirst = nullptr, *gptr = nullptr;
+  int* idx_s = nullptr;
+  void* val_s = nullptr;
   auto scan = [&](const int64_t* cnt, int64_t* out, int64_t cntn) {
     size_t tb = 0;
     HCK(blk_scan(nullptr, &tb, cnt, out, cntn, c->st));
@@ -1180,6 +1241,7 @@ int build_sparse_view(scs_ctx* c, int64_t b) {
     ptrR = bscratch<int64_t>(c, BS_PTRR, nkR + 1);
     int64_t* rcnt = bscratch<int64_t>(c, BS_RCNT, n + 1);
     int64_t* rptr = bscratch<int64_t>(c, BS_RPTR, n + 1);
+    rptr_s = rptr;
     HCK(blk_slice_size(F.ptr, N, rows, n, R.nblk, cntR, c->st));
     HCK(csr_rows_size(c->rowptr, rows, n, rcnt, c->st));
     scan(cntR, ptrR, nkR + 1);
@@ -1201,6 +1263,8 @@ int build_sparse_view(scs_ctx* c, int64_t b) {
       uint32_t* rank = bscratch<uint32_t>(c, BS_RANK, nnzb);
       int* rowidx_b = bscratch<int>(c, BS_ROWIDX, nnzb);
       void* valT_b = bscratch<char>(c, BS_VALT, (size_t)nnzb * vs);
+      idx_s = idx_b;
+      val_s = val_b;
       HCK(csr_rows_gather(c->rowptr, c->colidx, c->val, f32, rows, n, rptr, idx_b, val_b, c->st));
       HCK(hipMemsetAsync(ccnt, 0, sizeof(int64_t) * (m + 1), c->st));
       HCK(csr_claim(rptr, idx_b, n, ccnt, rank, c->st));
@@ -1223,6 +1287,14 @@ int build_sparse_view(scs_ctx* c, int64_t b) {
     HCK(blk_pad(bcnt, nkC, f32, c->st));
     scan(bcnt, ptrC, nkC + 1);
     HCK(hipMemcpyAsync(&nnzpC, ptrC + nkC, sizeof(int64_t), hipMemcpyDeviceToHost, c->st));
+    if (ssv) {   // the unpadded cut of the same columns: it holds the batch's nnzb entries
+      int64_t* gcnt = bscratch<int64_t>(c, BS_GCNT, nkG + 1);
+      gfirst = bscratch<int64_t>(c, BS_GFIRST, nkG + 1);
+      gptr = bscratch<int64_t>(c, BS_GPTR, nkG + 1);
+      HCK(hipMemsetAsync(gcnt, 0, sizeof(int64_t) * (nkG + 1), c->st));
+      HCK(blk_count(colptr_b, rowidx_s, m, Gb.shift, gcnt, gfirst, c->st));
+      scan(gcnt, gptr, nkG + 1);
+    }
     sync(c);
   }
   // the view's bytes from its shapes (dalloc's sizes), to choose its slot before anything is allocated:
@@ -1230,9 +1302,13 @@ int build_sparse_view(scs_ctx* c, int64_t b) {
   const int nval = epilogue_blocks(v.Npad);
   auto ab = [](int64_t cnt, size_t eb) { return (int64_t)(std::max<int64_t>(cnt, 1) * (int64_t)eb); };
   const int64_t nR = n > 0 ? nkR + 1 : 1, nC = n > 0 ? nkC + 1 : 1;
+  const int64_t nG = n > 0 ? nkG + 1 : 1;
   const int64_t bytes = ab(v.Npad, 8) * 6 + ab((int64_t)R.nblk * v.Npad, 8) + ab(nval, 8) +
                         ab((int64_t)Cc.nblk * c->mpad, 8) + ab(nR, 8) + ab(nC, 8) + ab(nnzpR + 8, 2) +
-                        ab(nnzpR + 8, vs) + ab(nnzpC + 8, 2) + ab(nnzpC + 8, vs);
+                        ab(nnzpR + 8, vs) + ab(nnzpC + 8, 2) + ab(nnzpC + 8, vs) +
+                        (ssv ? ab(n + 1, 8) + ab(nnzb, 4) + ab(nnzb, vs) + ab(nG, 8) + ab(nnzb + 8, 2) +
+                                   ab(nnzb + 8, vs)
+                             : 0);
   const int old = c->bplan.refill_target(n, ng, bytes);
   if (old >= 0) {
     free_view(c, c->spool[old]);
@@ -1270,6 +1346,29 @@ int build_sparse_view(scs_ctx* c, int64_t b) {
     HCK(blk_slice_copy(F.ptr, F.lidx, F.val, f32, N, rows, n, R.nblk, R.ptr, R.lidx, R.val, c->st));
     HCK(blk_scatter(colptr_b, rowidx_s, valT_s, f32, m, Cc.shift, Cc.ptr, bfirst, Cc.lidx, Cc.val, c->st));
   }
+  if (ssv) {
+    v.rowptr = dalloc<int64_t>(c, n + 1, n == 0);
+    v.colidx = dalloc<int>(c, nnzb, false);
+    v.val = dalloc<char>(c, (size_t)std::max<int64_t>(nnzb, 1) * vs, false);
+    Gb.nnz = nnzb;
+    Gb.ptr = dalloc<int64_t>(c, nG, n == 0);
+    Gb.lidx = dalloc<uint16_t>(c, nnzb + 8, false);
+    Gb.val = dalloc<char>(c, (size_t)(nnzb + 8) * vs, false);
+    // the +8 tail is read (never added) by the walks' idle lanes
+    HCK(hipMemsetAsync(Gb.lidx + nnzb, 0, 8 * sizeof(uint16_t), c->st));
+    HCK(hipMemsetAsync((char*)Gb.val + (size_t)nnzb * vs, 0, 8 * vs, c->st));
+    if (n > 0) {
+      HCK(hipMemcpyAsync(v.rowptr, rptr_s, sizeof(int64_t) * (n + 1), hipMemcpyDeviceToDevice, c->st));
+      HCK(hipMemcpyAsync(Gb.ptr, gptr, sizeof(int64_t) * nG, hipMemcpyDeviceToDevice, c->st));
+    }
+    if (nnzb > 0) {
+      HCK(hipMemcpyAsync(v.colidx, idx_s, sizeof(int) * nnzb, hipMemcpyDeviceToDevice, c->st));
+      HCK(hipMemcpyAsync(v.val, val_s, (size_t)nnzb * vs, hipMemcpyDeviceToDevice, c->st));
+      HCK(blk_scatter(colptr_b, rowidx_s, valT_s, f32, m, Gb.shift, Gb.ptr, gfirst, Gb.lidx, Gb.val, c->st));
+    }
+  } else {
+    Gb = SpBlkT();
+  }
   v.nnz = nnzb;
   v.bcsr = R;
   v.bcsc = Cc;
@@ -1294,6 +1393,7 @@ int build_sparse_view(scs_ctx* c, int64_t b) {
   c->bplan.slots[k].bytes = actual;
   if (fresh) c->spool.push_back(v);
   else c->spool[k] = v;
+  c->spool_kind = ssv ? 2 : 1;
   return k;
 }
 
@@ -1308,13 +1408,16 @@ void select_batch(scs_ctx* c, int64_t b) {
   if (b < 0) return;
   // f(A, y, x) = 1/2 x'(A x) + y'x reads A as an m x m operator, not as samples
   if (c->loss == SCS_LOSS_QUADRATIC) fail(c, SCS_ERR_ARG, "the quadratic loss has no samples to batch");
-  if (c->sparse_batches && c->sparse && c->method_set && c->method == SCS_PROX_LQNSCORE) {
+  const int64_t n = c->boff[b + 1] - c->boff[b], ng = c->bglob[b];
+  const int kind = c->method_set ? batch_view_kind(c, c->method) : 0;
+  c->vkind = kind;
+  // (kind 2: a batch of the feature branch, n_b + 1 > m, keeps the dense view and the m x m Gram)
+  if (kind == 1 || (kind == 2 && ng + 1 <= c->m)) {
     int ks = c->bplan.find(b);
-    if (ks < 0) ks = build_sparse_view(c, b);
+    if (ks < 0) ks = build_sparse_view(c, b, kind == 2);
     c->spview = ks;
     return;
   }
-  const int64_t n = c->boff[b + 1] - c->boff[b], ng = c->bglob[b];
   int k = -1;
   for (int i = 0; i < (int)c->bpool.size(); ++i)
     if (c->bpool[i].N == n && c->bpool[i].Nglob == ng) k = i;
@@ -2525,12 +2628,79 @@ void ggn_sample_direction_sharded(scs_ctx* c, const double* xh) {
   ggn_sample_direction(c, xh);
 }
 
+// The sparse sample-space branch (scs_set_sparse_sample): P from the nonzeros, no mirror, no Aᵀ copy
+bool sparse_sample_path(const scs_ctx* c) { return c->sparse_sample && c->sparse && !sharded(c); }
+
+SampleSys& sample_sys(scs_ctx* c, int64_t N) {
+  for (SampleSys& S : c->ssys)
+    if (S.N == N) return S;
+  c->ssys.emplace_back();   // filled in place: free_sample_sys gives a failed allocation's part back
+  SampleSys& S = c->ssys.back();
+  S.N = N;
+  S.NpS = round_up(N, 128);
+  S.n1pad = round_up(N + 1, 128);
+  S.Ps = dalloc<double>(c, (size_t)S.NpS * S.NpS);
+  S.Ms = dalloc<double>(c, (size_t)S.n1pad * S.n1pad);
+  S.bS = dalloc<double>(c, S.n1pad);
+  S.uN = dalloc<double>(c, round_up(std::max<int64_t>(N, 1), 16));
+  S.hvec = dalloc<double>(c, c->mpad);
+  S.hg = dalloc<double>(c, c->mpad);
+  return S;
+}
+
+// The Gram-blocked copy of the CSC (the column side of build_gram_blocked): the sorted columns cut
+// into 2^sparse_gram_shift()-wide blocks of rows, unpadded.  A batch view brings its own.
+void build_sample_blocked(scs_ctx* c) {
+  scs_ctx::SpBlk& B = c->sgram;
+  const int64_t ncols = c->m;
+  B.shift = sparse_gram_shift();
+  B.nblk = (int)std::max<int64_t>(ceil_div(c->N, int64_t(1) << B.shift), 1);
+  const int64_t nk = (int64_t)B.nblk * ncols;
+  int64_t* cnt = dalloc<int64_t>(c, nk + 1);
+  int64_t* first = dalloc<int64_t>(c, nk + 1);
+  B.ptr = dalloc<int64_t>(c, nk + 1);
+  HCK(blk_count(c->colptr, c->rowidx, ncols, B.shift, cnt, first, c->st));
+  size_t tb = 0;
+  HCK(blk_scan(nullptr, &tb, cnt, B.ptr, nk + 1, c->st));
+  void* tmp = dalloc<char>(c, tb);
+  HCK(blk_scan(tmp, &tb, cnt, B.ptr, nk + 1, c->st));
+  int64_t nnz = 0;
+  HCK(hipMemcpyAsync(&nnz, B.ptr + nk, sizeof(int64_t), hipMemcpyDeviceToHost, c->st));
+  sync(c);
+  dfree(c, tmp);
+  B.nnz = nnz;
+  B.lidx = dalloc<uint16_t>(c, nnz + 8);
+  B.val = c->sp_f32 ? (void*)dalloc<float>(c, (size_t)nnz + 8) : (void*)dalloc<double>(c, (size_t)nnz + 8);
+  HCK(blk_scatter(c->colptr, c->rowidx, c->valT, c->sp_f32, ncols, B.shift, B.ptr, first, B.lidx, B.val, c->st));
+  sync(c);
+  dfree_t(c, cnt);
+  dfree_t(c, first);
+}
+
+// P = A diag(h) Aᵀ (upper triangle, ld NpS) of the sparse rows in place, from their nonzeros
+void sparse_sample_gram(scs_ctx* c, const double* h, double* Ps, int64_t NpS) {
+  // (the shift is read per call for A/B tests; a batch view in place keeps the shift it was built with)
+  if (c->spview >= 0 && !c->sgram.ptr) fail(c, SCS_ERR_STATE, "internal: this batch view holds no sample-space copy");
+  if (!c->sgram.ptr || (c->spview < 0 && c->sgram.shift != sparse_gram_shift())) {
+    sync(c);
+    dfree_t(c, c->sgram.ptr);
+    dfree_t(c, c->sgram.lidx);
+    dfree(c, c->sgram.val);
+    build_sample_blocked(c);
+  }
+  const scs_ctx::SpBlk& B = c->sgram;
+  HCK(launch_sparse_sample_gram(c->rowptr, c->colidx, c->val, B.ptr, B.lidx, B.val, B.nnz, c->sp_f32, h, c->N, c->m,
+                                B.shift, Ps, NpS, c->st));
+  c->gram_kname = sparse_sample_kernel_name(c->sp_f32, B.nnz);
+}
+
 void ggn_sample_direction(scs_ctx* c, const double* xh) {
   const int64_t N = c->N, m = c->m;
   if (sharded(c)) return ggn_sample_direction_sharded(c, xh);
-  if (c->At && c->loss == SCS_LOSS_CALLBACK)   // the caller's J changes every step
+  const bool sps = sparse_sample_path(c);
+  if (!sps && c->At && c->loss == SCS_LOSS_CALLBACK)   // the caller's J changes every step
     HCK(launch_transpose(c->A, c->a32, c->Npad, N, m, c->At, c->mpad, c->NpS, c->st));
-  if (!c->At) {
+  if (!sps && !c->At) {
     const double* A = dense_A(c);
     c->NpS = round_up(N, 128);
     c->At = dalloc<double>(c, (size_t)c->NpS * c->mpad);
@@ -2550,30 +2720,40 @@ void ggn_sample_direction(scs_ctx* c, const double* xh) {
     HCK(hipMemcpyAsync(c->stiles, tl.data(), sizeof(int2) * nt, hipMemcpyHostToDevice, c->st));
     c->nstiles = nt;
   }
+  // the system scratch: the view's own, or (sparse branch) the set kept for this size
+  SampleSys own;
+  own.NpS = c->NpS, own.n1pad = c->n1pad;
+  own.Ps = c->Ps, own.Ms = c->Ms, own.bS = c->bS, own.uN = c->uN, own.hvec = c->hvec, own.hg = c->hg;
+  const SampleSys& S = sps ? sample_sys(c, N) : own;
+  double *const Ps = S.Ps, *const Ms = S.Ms, *const bS = S.bS, *const uN = S.uN, *const hvec = S.hvec, *const hg = S.hg;
+  const int64_t NpS = S.NpS, n1pad = S.n1pad;
   // s, q, r (prox-GGN-SCORE.jl:44-56) -> gN, hN, wN (a callback loss filled them: ggn_cb_load)
   if (c->loss != SCS_LOSS_CALLBACK) forward(c, xh, c->x, EPI_GGN | EPI_SQR, false);
-  HCK(launch_ggn_sample_prep(c->Hr, c->gr, c->lam, m, c->mpad, c->hvec, c->hg, c->st));
+  HCK(launch_ggn_sample_prep(c->Hr, c->gr, c->lam, m, c->mpad, hvec, hg, c->st));
   hipEvent_t e0;
   tbegin(c, T_GRAM, &e0);
-  HCK(gram_launch_gen(c->At, c->mpad, c->At, c->mpad, c->hvec, 0, c->mpad, c->stiles, c->nstiles, c->Ps, c->NpS,
-                      /*GRAM_UPPER*/ 4, c->st));
+  if (sps)
+    sparse_sample_gram(c, hvec, Ps, NpS);
+  else
+    HCK(gram_launch_gen(c->At, c->mpad, c->At, c->mpad, hvec, 0, c->mpad, c->stiles, c->nstiles, Ps, NpS,
+                        /*GRAM_UPPER*/ 4, c->st));
   tend(c, T_GRAM, e0);
-  HCK(launch_symmetrize(c->Ps, c->NpS, N, c->st));
-  const int ns = matvec_n(c, c->hg, c->nsplit);   // u = A (h∘λgr)
+  HCK(launch_symmetrize(Ps, NpS, N, c->st));
+  const int ns = matvec_n(c, hg, c->nsplit);   // u = A (h∘λgr)
   HCK(launch_epilogue(SCS_LOSS_LEAST_SQUARES, SCS_GGN_NONE, EPI_Z, c->zpart, ns, c->Npad, c->y, N, c->Npad, 1.0,
-                      c->uN, nullptr, nullptr, nullptr, nullptr, c->valpart, c->st));
-  HCK(launch_ggn_sample_assemble(c->Ps, c->NpS, c->gN, c->hN, c->wN, c->uN, nullptr, N, c->Ms, c->n1pad, c->bS,
+                      uN, nullptr, nullptr, nullptr, nullptr, c->valpart, c->st));
+  HCK(launch_ggn_sample_assemble(Ps, NpS, c->gN, c->hN, c->wN, uN, nullptr, N, Ms, n1pad, bS,
                                       c->st));
   tbegin(c, T_SOLVE, &e0);
-  const int64_t n1 = N + 1, np1 = c->n1pad;
+  const int64_t n1 = N + 1, np1 = n1pad;
   int info = 0;
   // NaN / Inf in the system: the reference's qr(...) \ b comes out NaN (no SingularException)
   HCK(hipMemsetAsync(c->cinfo, 0, sizeof(int), c->st));
-  HCK(launch_nonfinite(c->Ms, np1, n1, c->bS, c->cinfo, c->st));
+  HCK(launch_nonfinite(Ms, np1, n1, bS, c->cinfo, c->st));
   HCK(hipMemcpyAsync(&info, c->cinfo, sizeof(int), hipMemcpyDeviceToHost, c->st));
   sync(c);
   if (info != 0) {
-    HCK(launch_fill(c->bS, n1, std::numeric_limits<double>::quiet_NaN(), c->st));
+    HCK(launch_fill(bS, n1, std::numeric_limits<double>::quiet_NaN(), c->st));
   } else if (c->solver == SCS_SOLVER_REFERENCE) {
     // qr(I + A) \ residual (prox-GGN-SCORE.jl:126): the row-major system transposed into a
     // column-major copy with identity padding, Householder QR
@@ -2582,21 +2762,21 @@ void ggn_sample_direction(scs_ctx* c, const double* xh) {
       c->qrM = dalloc<double>(c, (size_t)np1 * np1);
       c->qrM_n = np1;
     }
-    HCK(qr_from_rowmajor(c->Ms, np1, c->qrM, np1, n1, np1, c->st));
-    qr_run(c, c->qrM, np1, c->bS);
+    HCK(qr_from_rowmajor(Ms, np1, c->qrM, np1, n1, np1, c->st));
+    qr_run(c, c->qrM, np1, bS);
   } else {
     HCK(lu_aux_init(&c->lu, np1, c->st));
-    info = lu_factor_checked(c, c->Ms, np1, n1, np1, c->cinfo, [&] {   // the system assembled again
-      HCK(launch_ggn_sample_assemble(c->Ps, c->NpS, c->gN, c->hN, c->wN, c->uN, nullptr, N, c->Ms, c->n1pad, c->bS,
+    info = lu_factor_checked(c, Ms, np1, n1, np1, c->cinfo, [&] {   // the system assembled again
+      HCK(launch_ggn_sample_assemble(Ps, NpS, c->gN, c->hN, c->wN, uN, nullptr, N, Ms, n1pad, bS,
                                      c->st));
     });
     if (info != 0) fail(c, SCS_ERR_SOLVE, "SingularException(%d)", info);
-    HCK(lu_solve(c->Ms, np1, np1, &c->lu, c->bS, c->st));
+    HCK(lu_solve(Ms, np1, np1, &c->lu, bS, c->st));
   }
   tend(c, T_SOLVE, e0);
-  HCK(launch_ggn_sample_scale(c->gN, c->bS, N, c->Npad, c->vN, c->st));
+  HCK(launch_ggn_sample_scale(c->gN, bS, N, c->Npad, c->vN, c->st));
   gemv_t_local(c, c->vN, c->gtmp);   // Aᵀ(s∘B)
-  HCK(launch_ggn_sample_direction(c->hvec, c->gtmp, c->hg, c->bS, N, m, c->d, c->st));
+  HCK(launch_ggn_sample_direction(hvec, c->gtmp, hg, bS, N, m, c->d, c->st));
 }
 
 // host column-major rows (N x m, lda) -> panel-blocked dst (Npad x mpad), one 128-column panel
@@ -2688,6 +2868,8 @@ void step_newton(scs_ctx* c, const double* xh, int64_t iter, double* x_new, doub
   const bool sample_space = (c->method == SCS_PROX_GGNSCORE) &&
                             (cbggn ? c->cb_nout + 1 <= m : (c->Nglob + 1 <= m && c->ggn != SCS_GGN_NONE));
   if (cbggn) ggn_cb_load(c, xh, sample_space);
+  // a sparse batch view holds what the sample space reads, not the m x m Gram's arrays
+  if (c->spview >= 0 && !sample_space) fail(c, SCS_ERR_STATE, "a sparse batch view serves the GGN sample-space branch only");
   if (sample_space) {
     if (cbggn) {
       CbScope scope(c);
@@ -3094,7 +3276,7 @@ static void reset_data(scs_ctx* c) {
   dfree_t(c, c->rowidx);
   dfree(c, c->val);
   dfree(c, c->valT);
-  for (auto* B : {&c->bcsr, &c->bcsc, &c->bgram}) {
+  for (auto* B : {&c->bcsr, &c->bcsc, &c->bgram, &c->sgram}) {
     dfree_t(c, B->ptr);
     dfree_t(c, B->lidx);
     dfree(c, B->val);
@@ -3363,6 +3545,30 @@ int scs_set_sparse_batches(scs_ctx* c, int on) {
     free_dense_views(c);   // the pooled views go, the registered list stays
     free_sparse_views(c);
     invalidate_caches(c);
+    if (c->bsel >= 0) select_batch(c, c->bsel);
+    sync(c);
+  });
+}
+
+int scs_set_sparse_sample(scs_ctx* c, int on) {
+  if (is_group(c)) return group_run(c, [&](scs_ctx* s_, int) { return scs_set_sparse_sample(s_, on); });
+  return guarded(c, [&] {
+    const int v = on ? 1 : 0;
+    if (v == c->sparse_sample) return;
+    HCK(hipSetDevice(c->dev));
+    sync(c);
+    c->sparse_sample = v;
+    // the views follow the mode (the registered list stays); the other mode's sample-space scratch goes
+    free_dense_views(c);
+    free_sparse_views(c);
+    free_sample_sys(c);
+    if (c->sparse) {
+      for (double** p : {&c->At, &c->Ps, &c->Ms, &c->bS, &c->uN, &c->hvec, &c->hg, &c->Ad}) dfree_t(c, *p);
+      dfree_t(c, c->stiles);
+      c->nstiles = 0;
+    }
+    invalidate_caches(c);
+    if (c->method_set) c->vkind = batch_view_kind(c, c->method);
     if (c->bsel >= 0) select_batch(c, c->bsel);
     sync(c);
   });
@@ -4310,13 +4516,17 @@ int scs_method_init(scs_ctx* c, int method, int ss_type, int use_prox, int mem) 
     invalidate_caches(c);
     // scs_set_sparse_batches: a pool view is sparse (ProxLQNSCORE) or dense (the Gram methods); views of
     // the other kind go, and a selected batch gets its view of the right kind
+    // (scs_set_sparse_sample: ProxGGNSCORE's sparse views also hold what the sample space reads, so
+    // ProxLQNSCORE's views do not serve it; its batches of the feature branch stay dense)
     if (c->sparse_batches && c->sparse) {
-      const bool sp = method == SCS_PROX_LQNSCORE;
-      const bool drop = sp ? !c->bpool.empty() : !c->spool.empty();
-      if (drop) {
+      const int kind = batch_view_kind(c, method);
+      const bool drop_dense = !c->bpool.empty() && (kind == 1 || (kind == 2 && c->vkind != 2));
+      const bool drop_sparse = !c->spool.empty() && c->spool_kind != kind;
+      c->vkind = kind;
+      if (drop_dense || drop_sparse) {
         sync(c);
-        if (sp) free_dense_views(c);
-        else free_sparse_views(c);
+        if (drop_dense) free_dense_views(c);
+        if (drop_sparse) free_sparse_views(c);
         if (c->bsel >= 0) select_batch(c, c->bsel);
       }
     }
@@ -5001,6 +5211,70 @@ int scs_gram_eval(scs_ctx* c, const double* w, double* G, int64_t ldg) {
     HCK(launch_symmetrize(c->G, c->mpad, c->m, c->st));
     HCK(hipMemcpy2DAsync(G, sizeof(double) * ldg, c->G, sizeof(double) * c->mpad, sizeof(double) * c->m, c->m,
                          hipMemcpyDeviceToHost, c->st));
+    sync(c);
+    if (c->timing) tresolve(c);
+  });
+}
+
+// P = A diag(h) Aᵀ of the selected batch or the full data, by the path a ProxGGNSCORE step takes: from
+// the nonzeros (scs_set_sparse_sample on a sparse A), else the Aᵀ copy (of the mirror) on the MFMA tiles
+int scs_sample_gram_eval(scs_ctx* c, const double* h, double* P, int64_t ldp) {
+  return guarded(c, [&] {
+    if (!c->has_data || c->generic) fail(c, SCS_ERR_STATE, "no data");
+    if (sharded(c)) fail(c, SCS_ERR_ARG, "scs_sample_gram_eval runs on one rank");
+    if (!h || !P) fail(c, SCS_ERR_ARG, "scs_sample_gram_eval: null argument");
+    HCK(hipSetDevice(c->dev));
+    BatchScope scope(c);
+    const int64_t N = c->N, m = c->m;
+    if (ldp < N) fail(c, SCS_ERR_ARG, "scs_sample_gram_eval: ldp %lld < N %lld", (long long)ldp, (long long)N);
+    const bool sps = sparse_sample_path(c);
+    const int64_t NpS = round_up(N, 128);
+    std::vector<double> hp(c->mpad, 0.0);
+    std::memcpy(hp.data(), h, sizeof(double) * m);
+    double* hd = dalloc<double>(c, c->mpad, false);
+    double *Ps = nullptr, *Pown = nullptr, *At = nullptr;   // Ps: the size's kept set, or Pown
+    int2* tiles = nullptr;
+    struct Free {
+      scs_ctx* c;
+      double **a, **b, **d;
+      int2** t;
+      ~Free() {
+        (void)hipStreamSynchronize(c->st);
+        dfree_t(c, *a);
+        dfree_t(c, *b);
+        dfree_t(c, *d);
+        dfree_t(c, *t);
+      }
+    } fr{c, &hd, &Pown, &At, &tiles};
+    h2d(c, hd, hp.data(), c->mpad);
+    if (sps) {
+      Ps = sample_sys(c, N).Ps;
+    } else {
+      Ps = Pown = dalloc<double>(c, (size_t)NpS * NpS);
+    }
+    hipEvent_t e0;
+    if (sps) {
+      tbegin(c, T_GRAM, &e0);
+      sparse_sample_gram(c, hd, Ps, NpS);
+      tend(c, T_GRAM, e0);
+    } else {
+      const double* A = dense_A(c);
+      At = dalloc<double>(c, (size_t)NpS * c->mpad);
+      HCK(launch_transpose(A, dense_a32(c), c->Npad, N, m, At, c->mpad, NpS, c->st));
+      const int nb = (int)(NpS / 128);
+      std::vector<int2> tl((size_t)nb * (nb + 1) / 2 + 1);
+      int nt = 0;
+      gram_tile_list(nb, tl.data(), &nt);
+      tiles = dalloc<int2>(c, std::max(nt, 1));
+      HCK(hipMemcpyAsync(tiles, tl.data(), sizeof(int2) * nt, hipMemcpyHostToDevice, c->st));
+      tbegin(c, T_GRAM, &e0);
+      HCK(gram_launch_gen(At, c->mpad, At, c->mpad, hd, 0, c->mpad, tiles, nt, Ps, NpS, /*GRAM_UPPER*/ 4, c->st));
+      tend(c, T_GRAM, e0);
+    }
+    HCK(launch_symmetrize(Ps, NpS, N, c->st));
+    if (N > 0)
+      HCK(hipMemcpy2DAsync(P, sizeof(double) * ldp, Ps, sizeof(double) * NpS, sizeof(double) * N, N,
+                           hipMemcpyDeviceToHost, c->st));
     sync(c);
     if (c->timing) tresolve(c);
   });

@@ -1409,6 +1409,161 @@ hipError_t launch_sparse_gram(const int64_t* colptr, const int* rowidx, const vo
   return hipSuccess;
 }
 
+// ---- the GGN sample-space Gram P = A diag(h) Aᵀ priced by nnz (scs_set_sparse_sample) -------------
+// P is the sparse Gram above applied to Aᵀ: the CSR of A is the CSC of Aᵀ, so the walks run with the
+// roles exchanged.  An item is (sample i, block b of 2^shift samples, b·2^shift <= i); the wave walks
+// row i's stored entries (feature j, a_ij) in stored order, weighs them by h_j and adds column j's
+// segment in block b (the Gram-blocked copy of the CSC: bptr[b·m + j]) into the LDS accumulator.
+// P(k, i), k <= i, is the sum over row i's entries in stored order of (h_j a_ij) a_kj, written at
+// P[i·ldp + k] up to the end of i's 128-row diagonal tile -- the triangle launch_symmetrize reads.
+//
+// In this regime (n + 1 <= m) a segment is short -- n·nnz_row / m / blocks entries, ~41 at 2^14 rows of
+// C5 -- so the walks above, one segment per wave instruction, leave most lanes idle.  The packed walk
+// takes up to 64 of row i's entries a trip (lane u: entry u's scaled value and segment bounds), forms
+// the inclusive prefix sum of the segment lengths across the lanes and walks the concatenated
+// segments 64 entries a trip with every lane busy: lane t's entry q = t0 + t belongs to the first
+// segment whose inclusive sum exceeds q (bisection over the lanes' sums, six ds_bpermute).  Segments
+// lie along the lanes in stored order, and one ds_add_f64 applies same-address lanes in ascending
+// lane order (tools/probes/probe_ldsatomic_order.hip), so every P(k, i) sums the same products in
+// the same order as the plain walks: the result is theirs bit for bit.  Segment positions are 32
+// bits wide (a copy of 2^31 entries or more takes the plain walk).
+__device__ __forceinline__ double ssg_shfl(double v, int src) {
+  const int64_t b = __builtin_bit_cast(int64_t, v);
+  const int lo = __shfl((int)(uint32_t)(uint64_t)b, src), hi = __shfl((int)(uint32_t)((uint64_t)b >> 32), src);
+  return __builtin_bit_cast(double, (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo));
+}
+template <typename VT>
+__global__ __launch_bounds__(64) void sparse_sample_gram_kernel(const int64_t* __restrict__ rowptr,
+                                                                const int* __restrict__ colidx,
+                                                                const VT* __restrict__ val,
+                                                                const int64_t* __restrict__ bptr,
+                                                                const uint16_t* __restrict__ lidx,
+                                                                const VT* __restrict__ bval,
+                                                                const double* __restrict__ h, int64_t m, int64_t n,
+                                                                int shift, int64_t i0, double* __restrict__ P,
+                                                                int64_t ldp) {
+  constexpr int U = 4;              // trips of 64 concatenated entries in flight
+  __shared__ double acc[1 << 12];   // 32 KiB: five waves per CU, as the plain walks
+  const int lane = threadIdx.x;
+  const int BS = 1 << shift;
+  const int64_t t = (int64_t)blockIdx.x;
+  int64_t I = i0 >> shift, base = 0;
+  while (true) {
+    const int64_t cnt = (int64_t)BS * (I + 1);
+    if (t < base + cnt) break;
+    base += cnt;
+    ++I;
+  }
+  const int64_t loc = t - base;
+  const int64_t i = I * BS + loc % BS;   // items b-major within a sample block
+  const int b = (int)(loc / BS);
+  if (i >= n) return;
+  for (int k = lane; k < BS; k += 64) acc[k] = 0.0;
+  __syncthreads();
+  const int64_t p0 = rowptr[i], p1 = rowptr[i + 1];
+  const int64_t boff = (int64_t)b * m;
+  for (int64_t p = p0; p < p1; p += 64) {
+    double s = 0.0;
+    int st = 0, ln = 0;
+    if (p + lane < p1) {
+      const int j = colidx[p + lane];
+      s = h[j] * (double)val[p + lane];
+      const int64_t s0 = bptr[boff + j], s1 = bptr[boff + j + 1];
+      st = (int)s0;
+      ln = (int)(s1 - s0);
+    }
+    int incl = ln;   // inclusive prefix sum of the segment lengths (at most 64·4096)
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int up = __shfl_up(incl, d);
+      if (lane >= d) incl += up;
+    }
+    const int total = __builtin_amdgcn_readlane(incl, 63);
+    const int org = st - (incl - ln);   // entry q of the concatenation lies at org + q in the copy
+    for (int t0 = 0; t0 < total; t0 += 64 * U) {
+      double v[U], sv[U];
+      int ix[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int q = t0 + 64 * u + lane;
+        const bool on = q < total;
+        const int qq = on ? q : total - 1;
+        int lo = 0, hi = 63;   // the first lane whose inclusive sum exceeds qq (lane 63's is total)
+#pragma unroll
+        for (int step = 0; step < 6; ++step) {
+          const int mid = (lo + hi) >> 1;
+          const bool right = __shfl(incl, mid) <= qq;
+          lo = right ? mid + 1 : lo;
+          hi = right ? hi : mid;
+        }
+        const int pos = __shfl(org, lo) + qq;
+        sv[u] = ssg_shfl(s, lo);
+        ix[u] = -1;
+        v[u] = 0.0;
+        if (on) {
+          v[u] = (double)bval[pos];
+          ix[u] = lidx[pos];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        if (ix[u] >= 0) atomicAdd(&acc[ix[u]], sv[u] * v[u]);
+    }
+  }
+  __syncthreads();
+  // column i, rows [b·BS, min(b·BS + BS, end of i's diagonal tile))
+  const int64_t r0 = (int64_t)b * BS;
+  const int64_t rend = ((i >> 7) + 1) << 7;
+  const int64_t nr = (rend - r0 < BS) ? rend - r0 : BS;
+  double* col = P + i * ldp + r0;
+  for (int k = lane; k < nr; k += 64) col[k] = acc[k];
+}
+
+// SCS_SPARSE_SAMPLE_KERNEL: 0 the plain arm (the Gram-blocked walks above on the exchanged arrays),
+// 1 the packed walk; read per call (A/B tests)
+constexpr int SSG_DEFAULT_KERNEL = 0;
+int sparse_sample_kernel() {
+  const char* e = getenv("SCS_SPARSE_SAMPLE_KERNEL");
+  return e ? (atoi(e) != 0 ? 1 : 0) : SSG_DEFAULT_KERNEL;
+}
+
+const char* sparse_sample_kernel_name(int f32, int64_t entries) {
+  if (sparse_sample_kernel() == 1 && entries < ((int64_t)1 << 31))
+    return f32 ? "sparse_sample_gram_kernel<float>" : "sparse_sample_gram_kernel<double>";
+  return sparse_gram_kernel_name(f32, entries);
+}
+
+// rowptr / colidx / val: the CSR of A (n rows, m columns; entries of a row in any order, duplicates
+// kept); bptr / lidx / bval: the Gram-blocked copy of its CSC (m columns cut into 2^shift-wide blocks
+// of rows, `entries` entries + 8 readable ones); h: m weights; P: ldp >= round_up(n, 128) columns.
+hipError_t launch_sparse_sample_gram(const int64_t* rowptr, const int* colidx, const void* val, const int64_t* bptr,
+                                     const uint16_t* lidx, const void* bval, int64_t entries, int f32,
+                                     const double* h, int64_t n, int64_t m, int shift, double* P, int64_t ldp,
+                                     hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  if (shift > 12 || shift < 7) return hipErrorInvalidValue;
+  if (sparse_sample_kernel() != 1 || entries >= ((int64_t)1 << 31))
+    return launch_sparse_gram(rowptr, colidx, val, bptr, lidx, bval, entries, f32, h, m, n, shift, P, ldp, st);
+  const int64_t BS = (int64_t)1 << shift;
+  int64_t i0 = 0;
+  while (i0 < n) {   // launches of at most 2^30 items: one per run of sample blocks
+    int64_t i1 = i0;
+    while (i1 < n && sparse_gram_items(i0, i1 + BS, shift) < ((int64_t)1 << 30)) i1 += BS;
+    if (i1 == i0) i1 = i0 + BS;
+    const int64_t items = sparse_gram_items(i0, i1, shift);
+    if (f32)
+      hipLaunchKernelGGL(sparse_sample_gram_kernel<float>, dim3((unsigned)items), dim3(64), 0, st, rowptr, colidx,
+                         (const float*)val, bptr, lidx, (const float*)bval, h, m, n, shift, i0, P, ldp);
+    else
+      hipLaunchKernelGGL(sparse_sample_gram_kernel<double>, dim3((unsigned)items), dim3(64), 0, st, rowptr, colidx,
+                         (const double*)val, bptr, lidx, (const double*)bval, h, m, n, shift, i0, P, ldp);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    i0 = i1;
+  }
+  return hipSuccess;
+}
+
 // ---- synthetic generator ---------------------------------------------------
 __device__ __forceinline__ uint64_t smix_s(uint64_t z) {
   z += 0x9E3779B97F4A7C15ull;

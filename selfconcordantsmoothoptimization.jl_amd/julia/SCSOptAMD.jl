@@ -16,7 +16,7 @@ import SelfConcordantSmoothOptimization: step!, init!, ProximalMethod, ProxModel
 
 export DeviceProblem, configure!, iterate_device!, set_gram_cache!, set_solver!, rccl_unique_id, set_comm_rccl!,
        set_comm_callback!, set_test!, set_test_device!, set_compute_f32!, fallback_counts, data_info, samplewise,
-       set_sparse_batches!, batch_info
+       set_sparse_batches!, set_sparse_sample!, batch_info
 
 const lib = joinpath(@__DIR__, "..", "scsopt", "libscsopt.so")
 
@@ -331,9 +331,10 @@ function DeviceProblem(A::SparseMatrixCSC{Float64}, y::AbstractVector, x0::Vecto
                        L=nothing, sol::Vector{Float64}=zero(x0), C_set=nothing, P=nothing, device::Integer=0,
                        val_f32::Bool=false, N_global::Integer=size(A, 1), row0::Integer=0, Atest=nothing,
                        ytest=nothing, Ntest_global::Integer=0, test_row0::Integer=0,
-                       sparse_batches::Bool=false)
+                       sparse_batches::Bool=false, sparse_sample::Bool=false)
     ctx = create_ctx(device)
     sparse_batches && chk(ccall((:scs_set_sparse_batches, lib), Cint, (Ptr{Cvoid}, Cint), ctx, 1), ctx)
+    sparse_sample && chk(ccall((:scs_set_sparse_sample, lib), Cint, (Ptr{Cvoid}, Cint), ctx, 1), ctx)
     N, m = size(A)
     yv = Vector{Float64}(y)
     At = SparseMatrixCSC(transpose(A))
@@ -399,6 +400,15 @@ end
 # the batch is then the reference's Matrix(As')).  Changing the mode drops the pooled batch views.
 function set_sparse_batches!(model::DeviceProblem, on::Bool=true)
     chk(ccall((:scs_set_sparse_batches, lib), Cint, (Ptr{Cvoid}, Cint), model.ctx, on ? 1 : 0), model.ctx)
+    return model
+end
+
+# ProxGGNSCORE's sample-space branch (N + 1 <= m) on a sparse A forms P = A diag(1/Hr) Aᵀ from the nonzeros
+# (scs_set_sparse_sample; off by default: a dense mirror, an Aᵀ copy and MFMA tiles).  With
+# set_sparse_batches! also on, its batches with n_b + 1 <= m become sparse views.  No effect on a
+# sharded context or a dense A.  Changing the mode drops the pooled batch views.
+function set_sparse_sample!(model::DeviceProblem, on::Bool=true)
+    chk(ccall((:scs_set_sparse_sample, lib), Cint, (Ptr{Cvoid}, Cint), model.ctx, on ? 1 : 0), model.ctx)
     return model
 end
 

@@ -163,6 +163,7 @@ _SIGS = {
     "scs_set_batches": (C.c_int, [C.c_void_p, c_i64p, c_i64p, C.c_int64]),
     "scs_select_batch": (C.c_int, [C.c_void_p, C.c_int64]),
     "scs_set_sparse_batches": (C.c_int, [C.c_void_p, C.c_int]),
+    "scs_set_sparse_sample": (C.c_int, [C.c_void_p, C.c_int]),
     "scs_batch_info": (C.c_int, [C.c_void_p, c_i64p, c_i64p, c_i64p]),
     "scs_step": (C.c_int, [C.c_void_p, c_dp, c_dp, C.c_int64, c_dp, c_dp, c_dp]),
     "scs_step_grad": (C.c_int, [C.c_void_p, c_dp, c_dp, C.c_int64, c_dp, c_dp, c_dp, c_dp]),
@@ -173,6 +174,7 @@ _SIGS = {
     "scs_smoother_eval": (C.c_int, [C.c_void_p, c_dp, c_dp, c_dp]),
     "scs_prox_eval": (C.c_int, [C.c_void_p, c_dp, c_dp, C.c_double, C.c_double, c_dp]),
     "scs_gram_eval": (C.c_int, [C.c_void_p, c_dp, c_dp, C.c_int64]),
+    "scs_sample_gram_eval": (C.c_int, [C.c_void_p, c_dp, c_dp, C.c_int64]),
     "scs_gemv_t_eval": (C.c_int, [C.c_void_p, c_dp, c_dp]),
     "scs_gemv_n_eval": (C.c_int, [C.c_void_p, c_dp, c_dp]),
     "scs_solve_eval": (C.c_int, [C.c_void_p, c_dp, c_dp, c_dp, C.c_int, c_dp, C.POINTER(C.c_int)]),

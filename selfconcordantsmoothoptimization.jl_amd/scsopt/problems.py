@@ -96,7 +96,7 @@ class Problem:
     def __init__(self, *args, Atest=None, ytest=None, L=None, sol=None, C_set=None, P=None,
                  out_fn: Optional[OutFn] = None, name=None, device=0, comm=None, N_global=None, row0=0,
                  sparse_f32=False, devices=None, device_exchange="rccl", Ntest_global=None, test_row0=0,
-                 dense_f32=False, sparse_batches=False, _ctx=None):
+                 dense_f32=False, sparse_batches=False, sparse_sample=False, _ctx=None):
         if len(args) == 5:
             A, y, x0, f, lam = args
         elif len(args) == 3:
@@ -138,6 +138,8 @@ class Problem:
         self.dense_f32 = bool(dense_f32)
         if sparse_batches:   # a mode of the context: set before any batch view exists
             self.ctx.check(_lib.lib.scs_set_sparse_batches(self.ctx.h, 1))
+        if sparse_sample:
+            self.ctx.check(_lib.lib.scs_set_sparse_sample(self.ctx.h, 1))
         if comm is not None and comm.active and _ctx is None:
             comm.attach(self.ctx)
         if _ctx is None:
@@ -709,10 +711,12 @@ class Problem:
         (0-based, GLOBAL rows: on several ranks every rank passes the same list and keeps the rows
         it owns), gathered on the device as the As, ys of their step! calls (iterate.jl:205-207).
         None / [] clears the list.  f / get_reg stay on the full data."""
+        self._bsel, self._bsizes = -1, []
         if not batches:
             self.ctx.check(_lib.lib.scs_set_batches(self.ctx.h, None, None, 0))
             return
         rs = [np.asarray(b, dtype=np.int64).reshape(-1) for b in batches]
+        self._bsizes = [int(r.size) for r in rs]
         rows = np.ascontiguousarray(np.concatenate(rs))
         off = np.zeros(len(rs) + 1, dtype=np.int64)
         off[1:] = np.cumsum([r.size for r in rs])
@@ -729,6 +733,15 @@ class Problem:
         drops the pooled views; the registered list stays.  scs_set_sparse_batches."""
         self.ctx.check(_lib.lib.scs_set_sparse_batches(self.ctx.h, int(bool(on))))
 
+    def set_sparse_sample(self, on=True):
+        """Opt-in: ProxGGNSCORE's sample-space branch (N + 1 <= m) on a sparse A forms P = A diag(1/Hr) Aᵀ
+        from the nonzeros -- no dense mirror, no Aᵀ copy, no tiles; the (N+1)² system and its solve are
+        unchanged.  With set_sparse_batches also on, batches with n_b + 1 <= m become sparse views under
+        ProxGGNSCORE as well (a step on one equals the step of a Problem holding A[rows_b], y[rows_b]).
+        Stored without effect on a sharded or multi-device context and on a dense A.  Changing the mode
+        drops the pooled views.  scs_set_sparse_sample."""
+        self.ctx.check(_lib.lib.scs_set_sparse_sample(self.ctx.h, int(bool(on))))
+
     def batch_info(self):
         """(sparse batch views held, their device bytes, views built since set_batches) -- scs_batch_info."""
         nv, vb, bd = C.c_int64(), C.c_int64(), C.c_int64()
@@ -738,6 +751,7 @@ class Problem:
     def select_batch(self, b=-1):
         """The registered batch the following step! calls see as As, ys (-1: the full data)."""
         self.ctx.check(_lib.lib.scs_select_batch(self.ctx.h, int(b)))
+        self._bsel = int(b) if int(b) >= 0 else -1
 
     def _smoother_eval(self, hmu, x):
         x = np.ascontiguousarray(x, dtype=np.float64)
@@ -759,6 +773,18 @@ class Problem:
         G = np.zeros((self.m, self.m))
         self.ctx.check(_lib.lib.scs_gram_eval(self.ctx.h, dptr(w), dptr(G), self.m))
         return G.T.copy()  # column-major -> row-major (lower triangle valid)
+
+    def sample_gram(self, h):
+        """A diag(h) Aᵀ of the selected batch or the full data, by the path a ProxGGNSCORE sample-space step
+        takes (scs_sample_gram_eval); the full symmetric N x N matrix."""
+        h = np.ascontiguousarray(h, dtype=np.float64)
+        if h.shape != (self.m,):
+            raise ValueError(f"h must have length m = {self.m}")
+        sel = getattr(self, "_bsel", -1)
+        n = self.N if sel < 0 else self._bsizes[sel]   # the rows select_batch chose last
+        P = np.zeros((n, n))
+        self.ctx.check(_lib.lib.scs_sample_gram_eval(self.ctx.h, dptr(h), dptr(P), n))
+        return P
 
     def gemv_t(self, v):
         v = np.ascontiguousarray(v, dtype=np.float64)
