@@ -48,8 +48,11 @@ enum scs_loss_kind {
   SCS_LOSS_QUADRATIC = 4,       /* 1/2*(x'*(A*x)) + y'*x             test/test_algs.jl:90 */
   SCS_LOSS_ROSENBROCK = 5,      /* chained Rosenbrock, no data        README.md:49 */
   SCS_LOSS_CALLBACK = 6,        /* the caller's f / grad_fx / hess_fx (scs_set_loss_callback) */
-  SCS_LOSS_SAMPLEWISE = 7       /* f = sum_i l(y_i, a_i'x): the caller's l, dl/dz, d2l/dz2 on z = A*x
+  SCS_LOSS_SAMPLEWISE = 7,      /* f = sum_i l(y_i, a_i'x): the caller's l, dl/dz, d2l/dz2 on z = A*x
                                    (scs_set_loss_samplewise); the device keeps A and every product */
+  /* K = nout outputs (scs_set_outputs): x = vec(X), X d x K; Y N x K; Z = A*X, P = row softmax of Z */
+  SCS_LOSS_SOFTMAX_CE = 8,      /* -c*sum(Y .* log.(P)): multinomial logistic regression (Y need not be one-hot) */
+  SCS_LOSS_MULTI_LS = 9         /* 0.5*c*sum((A*X .- Y).^2): multi-target least squares */
 };
 
 /* (out_fn, f(y, ŷ)) pairs used by ProxGGNSCORE (prox-GGN-SCORE.jl:44-56).    */
@@ -57,8 +60,10 @@ enum scs_ggn_kind {
   SCS_GGN_NONE = 0,
   SCS_GGN_SIGMOID_CE = 1,       /* Mfunc = sigmoid(A*x), CE on ŷ   test/test_algs.jl:10-11 */
   SCS_GGN_LINEAR_LS = 2,        /* out_fn = A*x, 0.5*c*sum((ŷ-y).^2) README.md:233-239 */
-  SCS_GGN_SAMPLEWISE = 3        /* ŷ_i = φ(a_i'x), f = sum_i l(y_i, ŷ_i): the caller's dŷ/dz, df/dŷ, d2f/dŷ2
+  SCS_GGN_SAMPLEWISE = 3,       /* ŷ_i = φ(a_i'x), f = sum_i l(y_i, ŷ_i): the caller's dŷ/dz, df/dŷ, d2f/dŷ2
                                    (scs_set_loss_samplewise with has_ggn) */
+  SCS_GGN_LINEAR_SOFTMAX_CE = 4, /* out_fn = A*X (the logits), f(Y, ŷ) = -c*sum(Y .* log.(softmax(ŷ))): J = I_K ⊗ A */
+  SCS_GGN_LINEAR_MULTI_LS = 5   /* out_fn = A*X, 0.5*c*sum((ŷ .- Y).^2) */
 };
 
 /* reg_name strings of get_reg / invoke_prox (regularizers.jl:4-31,
@@ -240,6 +245,32 @@ int scs_set_loss_callback(scs_ctx* ctx, scs_loss_fn fn, void* user, int64_t ggn_
 typedef int (scs_samplewise_fn)(void* user, int what, int64_t n, const double* z, const double* y, double* val,
                                 double* d1, double* d2, double* s, void* stream);
 int scs_set_loss_samplewise(scs_ctx* ctx, scs_samplewise_fn* fn, void* user, int device_ptrs, int has_ggn);
+
+/* ---- multi-output targets (optim_loop! reads ny = size(model.y, 2), iterate.jl:106) -----------
+ * scs_set_outputs(ctx, nout), 2 <= nout <= 16, is called BEFORE the data door.  After it the m of
+ * scs_set_data / scs_set_data_f32 / scs_set_data_device is A's column count d; y is N x nout,
+ * column-major with leading dimension N (a host pointer, or for the device door a host or device
+ * one); every vector-length argument elsewhere (x0, x, x_star, bounds, groups, gradients, x_out)
+ * has nvar = d*nout entries: x = vec(X), X d x nout column-major, entry (j, l) at j + d*l.  The
+ * held-out doors take N x nout targets likewise.  The loss is SCS_LOSS_SOFTMAX_CE or
+ * SCS_LOSS_MULTI_LS (with SCS_GGN_LINEAR_SOFTMAX_CE / SCS_GGN_LINEAR_MULTI_LS for ProxGGNSCORE):
+ *   grad f = vec(Aᵀ R), R = c (s_i P_ik - Y_ik) | c (Z - Y), s_i = sum_k Y_ik;
+ *   block (k, l) of JᵀQJ = hess f is Aᵀ diag(w_kl) A, w_kl,i = c s_i (δ_kl P_ik - P_ik P_il) | c δ_kl,
+ * one weighted Gram of the unchanged kernel per pair k <= l (one in all for the least squares),
+ * placed into the order-nvar system.  A stays on the device as one N x d block (fp64 or fp32
+ * storage): the products A X and Aᵀ R read it once for all nout columns.
+ * Refused with SCS_ERR_ARG: nout outside 2..16 (nout = 0 clears the mode); with nout set: a
+ * sparse A (scs_set_sparse*, scs_gen_sparse), scs_gen_data, nranks > 1 and multi-device contexts,
+ * scs_set_batches, any other loss kind, and ProxGGNSCORE when N*nout + 1 <= d*nout (the reference
+ * then takes its sample-space branch, whose step differs: use the callback loss for it).  The mode
+ * persists across data doors, as scs_set_dense_f32 does.                                        */
+/* (With nout set scs_get_dims reports A's column count d as m, scs_get_data returns y as nr x nout
+ * with leading dimension nr, and the single-vector kernel-level doors -- scs_gemv_n_eval,
+ * scs_gemv_t_eval, scs_gram_eval, scs_solve_eval, scs_gram_atv_eval, scs_sample_gram_eval -- are
+ * refused: scs_multi_products_eval / scs_multi_system_eval below serve it.)                       */
+int scs_set_outputs(scs_ctx* ctx, int nout);
+/* nout (1 when unset) and nvar = the length of x.  Either pointer may be NULL.                   */
+int scs_get_outputs(scs_ctx* ctx, int* nout, int64_t* nvar);
 
 /* ---- data  (Problem(A, y, ...) -- problems.jl:61-81) --------------------- */
 /* Upload host A (column-major, N x m, leading dim lda) and y (N).  N is the
@@ -597,6 +628,15 @@ int scs_get_columns(scs_ctx* ctx, const int64_t* cols, int64_t ncols, double* ou
  * fuses it (*fused = 1): entries G(ij[2k], ij[2k+1]) for k < n, and Aᵀv (m).              */
 int scs_gram_atv_eval(scs_ctx* ctx, const double* w, const double* v, const int64_t* ij, int64_t n,
                       double* gvals, double* atv, int* fused);
+
+/* Multi-output kernel-level doors (a dense A; K need not equal the context's nout).  X: d x K and
+ * V: N x K, column-major; AX (N x K) = A X and ATV (d x K) = Aᵀ V, through the step's kernels.
+ * 1 <= K <= 16.  Either pair (X, AX) / (V, ATV) may be NULL.                                      */
+int scs_multi_products_eval(scs_ctx* ctx, int K, const double* X, const double* V, double* AX, double* ATV);
+/* The assembled system of a multi-output context at x (nvar entries): G = JᵀQJ (nvar x nvar,
+ * column-major, ldg >= nvar, both triangles) before λ diag Hr, g = vec(Aᵀ R) and *f = f(x).  Any
+ * output may be NULL.                                                                              */
+int scs_multi_system_eval(scs_ctx* ctx, const double* x, double* G, int64_t ldg, double* g, double* f);
 
 /* ---- timing ------------------------------------------------------------- */
 /* on = 0: off; 1: HIP events around every Gram / product / solve / step; n > 1: in

@@ -415,6 +415,33 @@ hipError_t launch_gen_xtrue(double* x, int64_t m, uint64_t seed, double density,
 hipError_t launch_gen_y(int kind, const double* z, double* y, int64_t N, int64_t row0, uint64_t seed,
                         hipStream_t st);
 
+// ---- multi.hip: K = nout outputs on one dense A (scs_set_outputs); X d x K, Y / Z / R / P N x K
+// column-major (device stride Npad); dpad = round_up(d, 128)
+// Xt[j*K + l] (dpad x K, zero beyond d) <- x = vec(X); Vt[n*K + l] (Npad x K) <- V (stride ldv)
+hipError_t launch_multi_pack_x(const double* x, int64_t d, int64_t dpad, int K, double* Xt, hipStream_t st);
+hipError_t launch_multi_pack_v(const double* V, int64_t ldv, int64_t Npad, int K, double* Vt, hipStream_t st);
+// Z-partials of A X: part[(split*K + l)*Npad + n], nsplit slices (gemv_n_splits(Npad, d))
+hipError_t launch_multi_ax(const void* A, int a32, int64_t S, int64_t Npad, int64_t dpad, int K, const double* Xt,
+                           int nsplit, double* part, hipStream_t st);
+// Aᵀ V partials part[(chunk*K + l)*dpad + j] over multi_atv_chunks(Npad) row chunks, then
+// out[j + d*l] = their sum in chunk order
+int multi_atv_chunks(int64_t Npad);
+hipError_t launch_multi_atv(const void* A, int a32, int64_t S, int64_t Npad, int64_t d, int64_t dpad, int K,
+                            const double* Vt, double* part, hipStream_t st);
+hipError_t launch_multi_atv_finalize(const double* part, int nchunk, int K, int64_t dpad, int64_t d, double* out,
+                                     hipStream_t st);
+// the epilogue of SCS_LOSS_SOFTMAX_CE / SCS_LOSS_MULTI_LS (EPI_* flags): z, g = R, h = P, s = Σ_k Y_ik and
+// epilogue_blocks(Npad) value partials
+hipError_t launch_multi_epilogue(int loss, int flags, int K, const double* zpart, int nsplit, const double* Y,
+                                 int64_t N, int64_t Npad, double c, double* z, double* g, double* h, double* s,
+                                 double* valpart, hipStream_t st);
+// w[n] = Q_n[k, l] (rows N..Npad zero)
+hipError_t launch_multi_weight(int loss, const double* P, const double* s, int k, int l, int64_t N, int64_t Npad,
+                               double c, double* w, hipStream_t st);
+// the d x d Gram Gd (upper triangle valid, leading dimension ldd) -> blocks (k, l) and (l, k) of G
+hipError_t launch_multi_place(const double* Gd, int64_t ldd, int64_t d, int k, int l, double* G, int64_t ldg,
+                              hipStream_t st);
+
 // ---- sparse.hip (LDS-blocked gathers; out[b*ldo + r] = Σ_{p in row r, block b} val[p] x[(b<<shift) + lidx[p]])
 int spmv_blk_shift(int64_t ncols);
 int spmv_pad_index();   // padding index of the blocked layouts (the SpMV's zero slot)

@@ -130,6 +130,16 @@ struct scs_ctx {
 
   // data
   int64_t N = 0, Npad = 0, m = 0, mpad = 0, Nglob = 0, row0 = 0;
+  // multi-output targets (scs_set_outputs): nout = K outputs share one dense A of dc columns (dcp: padded
+  // to whole panels); the variable count is m = dc·K.  nout = 0 (unset): dc = m, dcp = mpad.  The data
+  // view's column count (dc, dcp) serves the products, the Gram, the tile lists and the doors; m, mpad
+  // everything after the products.
+  int nout = 0;
+  int64_t dc = 0, dcp = 0;
+  double* mXt = nullptr;   // x = vec(X) repacked K-contiguous (dcp x K, zero beyond dc): launch_multi_pack_x
+  double* mVt = nullptr;   // an N x K operand of Aᵀ V repacked K-contiguous (grow-only, mVt_cap doubles)
+  int64_t mVt_cap = 0;
+  double* Gd = nullptr;    // one dc x dc weighted Gram (dcp²) before its placement into G
   int64_t Nglob_data = 0;   // N_global of the full data (Nglob follows the swapped-in view)
   int64_t nstage = 0;  // Npad / 16: stages of the panel-blocked A (common.h tiled_off)
   bool has_data = false;
@@ -647,6 +657,11 @@ void require_ready(scs_ctx* c, bool need_method) {
 // the exchange step is active: several ranks, or one rank with the exchange forced
 bool sharded(const scs_ctx* c) { return c->nranks > 1 || c->comm_force; }
 
+// scs_set_outputs: K outputs on one A (1 when unset); multi: the multi-output kernels (multi.hip) run
+int kout(const scs_ctx* c) { return c->nout ? c->nout : 1; }
+bool multi(const scs_ctx* c) { return c->nout >= 2; }
+bool multi_loss(int loss) { return loss == SCS_LOSS_SOFTMAX_CE || loss == SCS_LOSS_MULTI_LS; }
+
 // doubles of the in-place all-reduce payload: packed Gram tiles ‖ Aᵀv (GGN / NSCORE), the
 // m-vector (LQN), or the all-gather of the rows for the sharded GGN sample-space branch
 int64_t reduce_buffer_doubles(const scs_ctx* c) {
@@ -730,6 +745,8 @@ void alloc_mspace(scs_ctx* c) {
   c->xstar = dalloc<double>(c, mp);
   dfree_t(c, c->lqR);
   c->lqR = dalloc<double>(c, (size_t)LQ_NPART * LQ_G);
+  dfree_t(c, c->mXt);
+  if (multi(c)) c->mXt = dalloc<double>(c, (size_t)c->dcp * c->nout);
   if (!c->hscal) HCK(hipHostMalloc((void**)&c->hscal, 64 * sizeof(double), hipHostMallocDefault));
   if (!c->hserr) {
     HCK(hipHostMalloc((void**)&c->hserr, sizeof(int), hipHostMallocDefault));
@@ -744,9 +761,10 @@ void alloc_mspace(scs_ctx* c) {
 void alloc_nspace(scs_ctx* c) {
   if (c->generic) return;
   ++c->y_stamp;   // a new view: its y is (re)written by the caller of this function
-  c->nsplit = c->sparse ? c->bcsr.nblk : gemv_n_splits(c->Npad, c->m);
+  const int64_t K = kout(c);   // multi-output: Z, R, P are N x K (stride Npad), the partials K columns per slice
+  c->nsplit = c->sparse ? c->bcsr.nblk : gemv_n_splits(c->Npad, c->dc);
   c->nval = epilogue_blocks(c->Npad);
-  c->nchunk = c->sparse ? c->bcsc.nblk : gemv_t_chunks(c->Npad);
+  c->nchunk = c->sparse ? c->bcsc.nblk : multi(c) ? multi_atv_chunks(c->Npad) : gemv_t_chunks(c->Npad);
   dfree_t(c, c->zpart);
   dfree_t(c, c->z);
   dfree_t(c, c->gN);
@@ -755,14 +773,14 @@ void alloc_nspace(scs_ctx* c) {
   dfree_t(c, c->vN);
   dfree_t(c, c->valpart);
   dfree_t(c, c->tpart);
-  c->zpart = dalloc<double>(c, (size_t)c->nsplit * c->Npad);
-  c->z = dalloc<double>(c, c->Npad);
-  c->gN = dalloc<double>(c, c->Npad);
-  c->hN = dalloc<double>(c, c->Npad);
+  c->zpart = dalloc<double>(c, (size_t)c->nsplit * c->Npad * K);
+  c->z = dalloc<double>(c, c->Npad * K);
+  c->gN = dalloc<double>(c, c->Npad * K);
+  c->hN = dalloc<double>(c, c->Npad * K);
   c->wN = dalloc<double>(c, c->Npad);
   c->vN = dalloc<double>(c, c->Npad);
   c->valpart = dalloc<double>(c, c->nval);
-  c->tpart = dalloc<double>(c, (size_t)c->nchunk * c->mpad);
+  c->tpart = dalloc<double>(c, (size_t)c->nchunk * (multi(c) ? c->dcp * K : c->mpad));
 }
 
 void ensure_gram(scs_ctx* c) {
@@ -770,7 +788,10 @@ void ensure_gram(scs_ctx* c) {
   const int64_t mp = c->mpad;
   c->G = dalloc<double>(c, (size_t)mp * mp);
   c->Gc = dalloc<double>(c, (size_t)mp * mp);
-  const int nb = (int)(mp / 128);
+  // the Gram's tile lists and schedules cover the data view's columns (one dc x dc block of a
+  // multi-output system, placed by launch_multi_place); the solver's lists below the whole system
+  if (multi(c)) c->Gd = dalloc<double>(c, (size_t)c->dcp * c->dcp);
+  const int nb = (int)(c->dcp / 128);
   std::vector<int2> tl((size_t)nb * (nb + 1) / 2 + nb), ul;
   int nt = 0;
   const char* sq = std::getenv("SCS_GRAM_TALL");
@@ -961,7 +982,7 @@ void invalidate_caches(scs_ctx* c) {
 // a panel-blocked block of `rows` (padded) rows: bytes, and its allocation (a float block is kept
 // in the double-typed field, rows * mpad / 2 doubles; mpad % 128 == 0)
 size_t a_block_bytes(const scs_ctx* c, int64_t rows, int a32) {
-  return (size_t)rows * c->mpad * (a32 ? sizeof(float) : sizeof(double));
+  return (size_t)rows * c->dcp * (a32 ? sizeof(float) : sizeof(double));
 }
 double* alloc_A(scs_ctx* c, int64_t rows, int a32, bool zero = true) {
   return dalloc<double>(c, a_block_bytes(c, rows, a32) / sizeof(double), zero);
@@ -1465,6 +1486,8 @@ double loss_scale_value(scs_ctx* c, double s) {
     case SCS_LOSS_LOGISTIC_MARGIN: return c->scale * s;
     case SCS_LOSS_LOGISTIC_CE: return -c->scale * s;
     case SCS_LOSS_LEAST_SQUARES: return 0.5 * s * c->scale;
+    case SCS_LOSS_SOFTMAX_CE: return -c->scale * s;
+    case SCS_LOSS_MULTI_LS: return 0.5 * s * c->scale;
     default: return s;
   }
 }
@@ -1482,7 +1505,12 @@ int matvec_n(scs_ctx* c, const double* xd, int nsplit) {
     c->prod_kname = spmv_kernel_name(vk);
     return B.nblk;
   }
-  HCK(launch_gemv_n(c->A, c->a32, c->nstage, c->Npad, c->mpad, xd, nsplit, c->zpart, c->Npad, c->st));
+  if (multi(c)) {   // Z = A X: x = vec(X) repacked K-contiguous, then one pass over A for all K columns
+    HCK(launch_multi_pack_x(xd, c->dc, c->dcp, c->nout, c->mXt, c->st));
+    HCK(launch_multi_ax(c->A, c->a32, c->nstage, c->Npad, c->dcp, c->nout, c->mXt, nsplit, c->zpart, c->st));
+    return nsplit;
+  }
+  HCK(launch_gemv_n(c->A, c->a32, c->nstage, c->Npad, c->dcp, xd, nsplit, c->zpart, c->Npad, c->st));
   if (c->a32) c->prod_kname = GEMV_N_F32_NAME;
   return nsplit;
 }
@@ -1495,13 +1523,33 @@ int matvec_t_part(scs_ctx* c, const double* v) {
     HCK(launch_spmv_blk(B.ptr, B.lidx, B.val, vk, v, c->m, c->N, B.shift, c->nnz, c->tpart, c->mpad, c->st));
     return B.nblk;
   }
-  HCK(launch_gemv_t(c->A, c->a32, c->nstage, c->Npad, c->m, c->mpad, v, c->tpart, c->st));
+  if (multi(c)) fail(c, SCS_ERR_ARG, "internal: the single-vector Aᵀv partials do not serve a multi-output context");
+  HCK(launch_gemv_t(c->A, c->a32, c->nstage, c->Npad, c->dc, c->dcp, v, c->tpart, c->st));
   return c->nchunk;
+}
+
+// the grow-only K-contiguous copy of an N x K operand (launch_multi_pack_v)
+double* multi_vt(scs_ctx* c, int64_t need) {
+  if (c->mVt_cap < need) {
+    dfree_t(c, c->mVt);
+    c->mVt_cap = 0;
+    c->mVt = dalloc<double>(c, need);
+    c->mVt_cap = need;
+  }
+  return c->mVt;
 }
 
 // out (device, m) = Aᵀ v over the local rows (dense: chunked column sums +
 // fixed-order finalize; sparse: one CSC gather pass)
 void matvec_t(scs_ctx* c, const double* v, double* out) {
+  if (multi(c)) {   // vec(Aᵀ V), V N x K (stride Npad): chunk partials of all K columns in one pass over A
+    const int K = c->nout;
+    double* Vt = multi_vt(c, c->Npad * K);
+    HCK(launch_multi_pack_v(v, c->Npad, c->Npad, K, Vt, c->st));
+    HCK(launch_multi_atv(c->A, c->a32, c->nstage, c->Npad, c->dc, c->dcp, K, Vt, c->tpart, c->st));
+    HCK(launch_multi_atv_finalize(c->tpart, c->nchunk, K, c->dcp, c->dc, out, c->st));
+    return;
+  }
   const int np = matvec_t_part(c, v);
   HCK(launch_gemv_t_finalize(c->tpart, np, c->mpad, c->m, out, c->st));
 }
@@ -1543,6 +1591,13 @@ const double* sw_host_y(scs_ctx* c) {
 // cached c->z; one partial without EPI_Z is z already), (2) asks the caller's functions for exactly
 // what `flags` needs and (3) launches samplewise_epilogue_kernel over their output.
 void loss_epilogue(scs_ctx* c, int flags, const double* zpart, int ns, double* zout) {
+  if (multi(c)) {   // R -> gN, P -> hN (N x K, stride Npad), s_i = Σ_k Y_ik -> vN
+    if (!multi_loss(c->loss)) fail(c, SCS_ERR_ARG, "a multi-output context (scs_set_outputs) takes SCS_LOSS_SOFTMAX_CE or "
+                                                   "SCS_LOSS_MULTI_LS");
+    HCK(launch_multi_epilogue(c->loss, flags, c->nout, zpart, ns, c->y, c->N, c->Npad, c->scale, zout, c->gN, c->hN,
+                              c->vN, c->valpart, c->st));
+    return;
+  }
   if (c->loss != SCS_LOSS_SAMPLEWISE) {
     HCK(launch_epilogue(c->loss, c->ggn, flags, zpart, ns, c->Npad, c->y, c->N, c->Npad, c->scale, zout, c->gN, c->hN,
                         c->wN, c->vN, c->valpart, c->st));
@@ -1820,7 +1875,8 @@ bool ls_incremental(const scs_ctx* c) {
   const char* e = std::getenv("SCS_LS_INCR");   // read per call (A/B within one process)
   const bool off = e && e[0] == '0';
   return !off && !c->generic && (c->loss == SCS_LOSS_LOGISTIC_MARGIN || c->loss == SCS_LOSS_LOGISTIC_CE ||
-                                 c->loss == SCS_LOSS_LEAST_SQUARES || c->loss == SCS_LOSS_SAMPLEWISE);
+                                 c->loss == SCS_LOSS_LEAST_SQUARES || c->loss == SCS_LOSS_SAMPLEWISE ||
+                                 multi_loss(c->loss));
 }
 
 double line_search(scs_ctx* c, const double* xh, const double* xd, const double* dd) {
@@ -1838,13 +1894,14 @@ double line_search(scs_ctx* c, const double* xh, const double* xd, const double*
   if (incr) {
     // z0 = A x: f(x) above left it in c->z (forward with EPI_Z); A d once into zd
     forward(c, xh, xd, 0);
-    if (c->lscap < 3 * c->Npad) {
+    const int64_t nz = c->Npad * kout(c);   // a multi-output z is N x K: the pair is two slices of K columns
+    if (c->lscap < 3 * nz) {
       dfree_t(c, c->lsbuf);
-      c->lsbuf = dalloc<double>(c, 3 * c->Npad);
-      c->lscap = 3 * c->Npad;
+      c->lsbuf = dalloc<double>(c, 3 * nz);
+      c->lscap = 3 * nz;
     }
     pair = c->lsbuf;
-    zd = c->lsbuf + 2 * c->Npad;
+    zd = c->lsbuf + 2 * nz;
     hipEvent_t e0;
     tbegin(c, T_GEMV, &e0);
     const int ns = matvec_n(c, dd, c->nsplit);
@@ -1865,7 +1922,7 @@ double line_search(scs_ctx* c, const double* xh, const double* xd, const double*
     HCK(launch_trial_point(xd, dd, alpha, c->m, c->gtmp2, c->st));
     double ft;
     if (incr) {
-      HCK(launch_ls_pair(c->z, zd, alpha, c->Npad, pair, c->st));
+      HCK(launch_ls_pair(c->z, zd, alpha, c->Npad * kout(c), pair, c->st));
       loss_epilogue(c, EPI_VAL, pair, 2, nullptr);   // (a sample-wise trial's z goes to scratch, not over c->z)
       double* dst = sharded(c) ? c->red : c->scal + 14;
       HCK(launch_sum_partials(c->valpart, c->nval, dst, c->st));
@@ -2372,16 +2429,16 @@ void gram_main(scs_ctx* c, const double* w, double* out, int packed, const doubl
   const bool pr = c->ptiles && !(packed & 1);   // unpacked: the paired list
   const int nsplit = pr ? c->pnsplit : c->gnsplit;
   const int npiece = (v && c->gwork) ? std::max(nsplit, 1) : 1;
-  if (v && npiece > 1) HCK(hipMemsetAsync(c->vpart, 0, sizeof(double) * npiece * c->mpad, c->st));
+  if (v && npiece > 1) HCK(hipMemsetAsync(c->vpart, 0, sizeof(double) * npiece * c->dcp, c->st));
   if (c->gwork)
     HCK(gram_launch_sched(A, dense_a32(c), c->nstage, w, c->Npad, pr ? c->pwork : c->gwork,
                           pr ? c->pseglen : c->gseglen, nsplit, pr ? c->pcomb : c->gcomb, pr ? c->pncomb : c->gncomb,
-                          c->gpart, out, c->mpad, packed, c->tall, c->st, v, c->vpart, c->mpad));
+                          c->gpart, out, c->dcp, packed, c->tall, c->st, v, c->vpart, c->dcp));
   else
     HCK(gram_launch(A, dense_a32(c), c->nstage, w, c->Npad, pr ? c->ptiles : c->tiles, pr ? c->nptiles : c->ntiles,
-                    out, c->mpad, packed, c->tall, c->st, v, c->vpart, c->mpad));
+                    out, c->dcp, packed, c->tall, c->st, v, c->vpart, c->dcp));
   c->gram_kname = gram_main_kernel_name();
-  if (v) HCK(gram_vfinal_launch(c->vpart, npiece, c->mpad, c->m, vout, c->st));
+  if (v) HCK(gram_vfinal_launch(c->vpart, npiece, c->dcp, c->dc, vout, c->st));
 }
 
 // Gram of the local rows with weights w -> c->G (single rank) or the packed
@@ -2784,9 +2841,9 @@ void ggn_sample_direction(scs_ctx* c, const double* xh) {
 // elements) are float; a32: dst's are -- fp64 rows into an fp32 dst are rounded in the retile step
 static void upload_panels(scs_ctx* c, const void* A, int in32, int64_t N, int64_t lda, int64_t Npad, double* dst,
                           int a32, double* C) {
-  const int64_t m = c->m;
+  const int64_t m = c->dc;
   const size_t es = in32 ? sizeof(float) : sizeof(double);
-  for (int64_t p = 0; p < c->mpad / 128; ++p) {
+  for (int64_t p = 0; p < c->dcp / 128; ++p) {
     const int64_t j0 = p * 128, nc = std::min<int64_t>(128, m - j0);
     HCK(hipMemsetAsync(C, 0, es * Npad * 128, c->st));
     if (nc > 0 && N > 0)
@@ -2859,6 +2916,61 @@ static void clear_gram_padding(scs_ctx* c) {
   HCK(hipMemset2DAsync(c->G + m, sizeof(double) * ld, 0, sizeof(double) * (ld - m), m, c->st));   // rows >= m
 }
 
+// ProxGGNSCORE on a multi-output context takes the feature branch only: with N·K + 1 <= d·K the
+// reference's sample-space branch (prox-GGN-SCORE.jl:124-127) gives another step
+void refuse_multi_sample_space(scs_ctx* c, int method) {
+  if (multi(c) && method == SCS_PROX_GGNSCORE && c->Nglob * c->nout + 1 <= c->m)
+    fail(c, SCS_ERR_ARG, "ProxGGNSCORE with scs_set_outputs (nout = %d): N*nout + 1 = %lld <= d*nout = %lld, where the "
+                         "reference takes its sample-space branch (H^-1 = 1/Hr without lambda: another step); the "
+                         "multi-output device path forms the feature branch only -- use the callback loss "
+                         "(losses.callback) for this shape", c->nout, (long long)(c->Nglob * c->nout + 1),
+         (long long)c->m);
+}
+
+// The order-d·K system of a multi-output loss at the point of the last forward(EPI_GGN) (P in hN, s in
+// vN): block (k, l) of JᵀQJ = ∇²f is Aᵀ diag(w_kl) A.  One weight vector at a time (never all
+// K(K+1)/2), the unchanged weighted Gram into Gd, then its placement as blocks (k, l) and (l, k).
+// Multi-target least squares: one Gram c·AᵀA on the K diagonal blocks, exact zeros elsewhere.
+void multi_system(scs_ctx* c) {
+  ensure_gram(c);
+  const int K = c->nout;
+  const int64_t ld = c->mpad;
+  hipEvent_t e0;
+  tbegin(c, T_GRAM, &e0);
+  if (c->loss == SCS_LOSS_MULTI_LS) {
+    HCK(hipMemsetAsync(c->G, 0, sizeof(double) * (size_t)ld * ld, c->st));
+    HCK(launch_multi_weight(c->loss, c->hN, c->vN, 0, 0, c->N, c->Npad, c->scale, c->wN, c->st));
+    gram_main(c, c->wN, c->Gd, 0);
+    for (int k = 0; k < K; ++k) HCK(launch_multi_place(c->Gd, c->dcp, c->dc, k, k, c->G, ld, c->st));
+  } else {
+    clear_gram_padding(c);
+    for (int k = 0; k < K; ++k)
+      for (int l = k; l < K; ++l) {
+        HCK(launch_multi_weight(c->loss, c->hN, c->vN, k, l, c->N, c->Npad, c->scale, c->wN, c->st));
+        gram_main(c, c->wN, c->Gd, 0);
+        HCK(launch_multi_place(c->Gd, c->dcp, c->dc, k, l, c->G, ld, c->st));
+      }
+  }
+  tend(c, T_GRAM, e0);
+}
+
+// ProxNSCORE / ProxGGNSCORE direction of a multi-output loss -> c->d.  ∇²f = JᵀQJ (J = I_K ⊗ A, the
+// output is linear in x), so both methods build the same system; rhs = vec(AᵀR) + λ gr.
+void multi_newton_direction(scs_ctx* c, const double* xh) {
+  const int64_t m = c->m;
+  refuse_multi_sample_space(c, c->method);
+  if (c->method == SCS_PROX_GGNSCORE && c->ggn == SCS_GGN_NONE)
+    fail(c, SCS_ERR_ARG, "ProxGGNSCORE needs an out_fn / GGN loss kind");
+  forward(c, xh, c->x, EPI_GGN, false);
+  gemv_t_local(c, c->gN, c->gtmp);
+  if (c->gfix && c->method == SCS_PROX_NSCORE) grad_f_dev(c, xh, c->x, c->gtmp);
+  multi_system(c);
+  HCK(launch_axpby(c->gtmp, c->lam, c->gr, m, c->gq, c->st));
+  HCK(launch_diag_add(c->G, c->mpad, m, c->lam, c->Hr, c->st));
+  solve_system(c, c->gq);
+  HCK(launch_neg(c->gq, m, c->d, c->st));
+}
+
 // ProxNSCORE / ProxGGNSCORE step
 void step_newton(scs_ctx* c, const double* xh, int64_t iter, double* x_new, double* dx, double* pri) {
   const int64_t m = c->m;
@@ -2870,7 +2982,9 @@ void step_newton(scs_ctx* c, const double* xh, int64_t iter, double* x_new, doub
   if (cbggn) ggn_cb_load(c, xh, sample_space);
   // a sparse batch view holds what the sample space reads, not the m x m Gram's arrays
   if (c->spview >= 0 && !sample_space) fail(c, SCS_ERR_STATE, "a sparse batch view serves the GGN sample-space branch only");
-  if (sample_space) {
+  if (multi(c)) {
+    multi_newton_direction(c, xh);
+  } else if (sample_space) {
     if (cbggn) {
       CbScope scope(c);
       ggn_sample_direction(c, xh);
@@ -3181,6 +3295,8 @@ int scs_set_comm(scs_ctx* c, int rank, int nranks, scs_allreduce_fn fn, void* us
   return guarded(c, [&] {
     if (nranks < 1 || rank < 0 || rank >= nranks) fail(c, SCS_ERR_ARG, "bad rank/nranks %d/%d", rank, nranks);
     if (nranks > 1 && !fn) fail(c, SCS_ERR_ARG, "nranks > 1 needs an all-reduce callback");
+    if (nranks > 1 && multi(c))
+      fail(c, SCS_ERR_ARG, "nranks > 1 is not supported with scs_set_outputs (nout = %d)", c->nout);
     if (c->rccl) {
       (void)ncclCommDestroy(c->rccl);
       c->rccl = nullptr;
@@ -3204,6 +3320,8 @@ int scs_set_comm_rccl(scs_ctx* c, int rank, int nranks, const void* id) {
   return guarded(c, [&] {
     if (nranks < 1 || rank < 0 || rank >= nranks || !id)
       fail(c, SCS_ERR_ARG, "bad rank/nranks %d/%d or null id", rank, nranks);
+    if (nranks > 1 && multi(c))
+      fail(c, SCS_ERR_ARG, "nranks > 1 is not supported with scs_set_outputs (nout = %d)", c->nout);
     HCK(hipSetDevice(c->dev));
     sync(c);
     if (c->rccl) {
@@ -3249,12 +3367,19 @@ int scs_set_reduce_buffer(scs_ctx* c, void* p, int64_t nd) {
   });
 }
 
+// the doors and kernel-level entry points that do not serve a multi-output context
+static void refuse_multi(scs_ctx* c, const char* what) {
+  if (multi(c)) fail(c, SCS_ERR_ARG, "%s is not supported with scs_set_outputs (nout = %d)", what, c->nout);
+}
+
 static void set_dims(scs_ctx* c, int64_t N, int64_t m, int64_t Nglob, int64_t row0) {
   if (m <= 0 || N < 0) fail(c, SCS_ERR_ARG, "bad dimensions N=%lld m=%lld", (long long)N, (long long)m);
   c->N = N;
-  c->m = m;
+  c->dc = m;   // the data view's columns; the variable count is dc·K with scs_set_outputs
+  c->dcp = round_up(m, 128);
+  c->m = m * kout(c);
   c->Npad = std::max<int64_t>(round_up(std::max<int64_t>(N, 1), 16), 16);
-  c->mpad = round_up(m, 128);
+  c->mpad = round_up(c->m, 128);
   c->nstage = c->Npad / 16;
   c->Nglob = Nglob > 0 ? Nglob : N;
   c->Nglob_data = c->Nglob;
@@ -3296,6 +3421,9 @@ static void reset_data(scs_ctx* c) {
   c->ring_rows = 0;
   c->ring_r0[0] = c->ring_r0[1] = -1;
   dfree_t(c, c->Gk);
+  dfree_t(c, c->Gd);
+  dfree_t(c, c->mVt);
+  c->mVt_cap = 0;
   free_view(c, c->cbv);
   dfree_t(c, c->cbstage);
   ++c->data_gen;
@@ -3440,10 +3568,16 @@ static void join_src_stream(scs_ctx* c, hipStream_t src_stream) {
 }
 
 // y of a device door: a host or a device pointer (the library asks the pointer's attributes)
+// (multi-output: N x K column-major with leading dimension N -> the view's stride Npad)
 static void copy_y_any(scs_ctx* c, const double* y, int64_t N) {
   if (!y || N <= 0) return;
   const bool ydev = is_device_ptr(y, nullptr);
-  HCK(hipMemcpyAsync(c->y, y, sizeof(double) * N, ydev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->st));
+  const hipMemcpyKind kind = ydev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  if (multi(c))
+    HCK(hipMemcpy2DAsync(c->y, sizeof(double) * c->Npad, y, sizeof(double) * N, sizeof(double) * N, c->nout, kind,
+                         c->st));
+  else
+    HCK(hipMemcpyAsync(c->y, y, sizeof(double) * N, kind, c->st));
 }
 
 // N rows of src -> the context's (current view's) A and y.  Host rows: panel by panel through the
@@ -3452,7 +3586,7 @@ static void copy_y_any(scs_ctx* c, const double* y, int64_t N) {
 static void load_dense(scs_ctx* c, const DenseSrc& s, int64_t N, const double* y) {
   if (s.dev) {
     join_src_stream(c, s.src_stream);
-    HCK(launch_tile_device(s.A, s.in32, s.sn, s.sm, N, c->m, c->Npad, c->mpad, c->A, c->a32, c->st));
+    HCK(launch_tile_device(s.A, s.in32, s.sn, s.sm, N, c->dc, c->Npad, c->dcp, c->A, c->a32, c->st));
     copy_y_any(c, y, N);
     sync(c);
     return;
@@ -3462,7 +3596,12 @@ static void load_dense(scs_ctx* c, const DenseSrc& s, int64_t N, const double* y
   upload_panels(c, s.A, s.in32, N, s.lda, c->Npad, c->A, c->a32, C);
   sync(c);
   dfree_t(c, C);
-  if (y) h2d(c, c->y, y, N);
+  if (y && multi(c)) {
+    copy_y_any(c, y, N);
+    sync(c);   // a pageable host source: the call returns with the copy done
+  } else if (y) {
+    h2d(c, c->y, y, N);
+  }
 }
 
 // scs_set_data (in32 = 0) / scs_set_data_f32 (in32 = 1: host floats, stored as they are) /
@@ -3477,6 +3616,13 @@ static int set_data_any(scs_ctx* c, int64_t N, int64_t m, const DenseSrc& src, c
   }
   return guarded(c, [&] {
     HCK(hipSetDevice(c->dev));
+    if (multi(c)) {
+      if (!A) fail(c, SCS_ERR_ARG, "scs_set_outputs (nout = %d) needs a dense A: a ProblemGeneric (A = NULL) has no outputs",
+                   c->nout);
+      if (c->nranks > 1 || (Nglob > 0 && Nglob != N) || row0 != 0)
+        fail(c, SCS_ERR_ARG, "scs_set_outputs (nout = %d) runs on one rank: nranks > 1 / a row shard is not supported",
+             c->nout);
+    }
     if (src.dev) check_device_src(c, src, N, m);
     if (A) refuse_f32_quadratic(c, in32 | c->dense_f32);
     if (in32 && A) c->dense_f32 = 1;
@@ -3487,7 +3633,7 @@ static int set_data_any(scs_ctx* c, int64_t N, int64_t m, const DenseSrc& src, c
       if (!src.dev && src.lda < N) fail(c, SCS_ERR_ARG, "lda (%lld) < N (%lld)", (long long)src.lda, (long long)N);
       c->a32 = c->dense_f32;
       c->A = alloc_A(c, c->Npad, c->a32, !src.dev);
-      c->y = dalloc<double>(c, c->Npad);
+      c->y = dalloc<double>(c, c->Npad * kout(c));
       load_dense(c, src, N, y);
     }
     alloc_mspace(c);
@@ -3635,6 +3781,7 @@ int scs_gen_data(scs_ctx* c, const scs_synth* s) {
   if (is_group(c)) return group_gen_data(c, s);
   return guarded(c, [&] {
     if (!s) fail(c, SCS_ERR_ARG, "null synth spec");
+    refuse_multi(c, "scs_gen_data (the synthetic generator has one target column)");
     HCK(hipSetDevice(c->dev));
     refuse_f32_quadratic(c, c->dense_f32);
     reset_data(c);
@@ -3664,8 +3811,8 @@ int scs_get_data(scs_ctx* c, int64_t r0, int64_t nr, double* A, int64_t lda_out,
     if (r0 < 0 || nr < 0 || r0 + nr > c->N) fail(c, SCS_ERR_ARG, "row range out of bounds");
     if (A && nr > 0) {
       double* C = dalloc<double>(c, (size_t)c->Npad * 128);
-      for (int64_t p = 0; p < c->mpad / 128; ++p) {
-        const int64_t j0 = p * 128, nc = std::min<int64_t>(128, c->m - j0);
+      for (int64_t p = 0; p < c->dcp / 128; ++p) {
+        const int64_t j0 = p * 128, nc = std::min<int64_t>(128, c->dc - j0);
         if (nc <= 0) break;
         HCK(launch_retile(C, 0, c->A, c->a32, c->Npad, p, 0, c->st));   // fp32-stored rows come back widened
         HCK(hipMemcpy2DAsync(A + j0 * lda_out, sizeof(double) * lda_out, C + r0, sizeof(double) * c->Npad,
@@ -3674,7 +3821,11 @@ int scs_get_data(scs_ctx* c, int64_t r0, int64_t nr, double* A, int64_t lda_out,
       sync(c);
       dfree_t(c, C);
     }
-    if (y && nr > 0) d2h(c, y, c->y + r0, nr);
+    if (y && nr > 0 && multi(c))   // nr x nout, column-major with leading dimension nr
+      HCK(hipMemcpy2DAsync(y, sizeof(double) * nr, c->y + r0, sizeof(double) * c->Npad, sizeof(double) * nr, c->nout,
+                           hipMemcpyDeviceToHost, c->st));
+    else if (y && nr > 0)
+      d2h(c, y, c->y + r0, nr);
     sync(c);
   });
 }
@@ -3689,7 +3840,7 @@ int scs_get_dims(scs_ctx* c, int64_t* N, int64_t* m, int64_t* Ng, int64_t* r0) {
   }
   return guarded(c, [&] {
     if (N) *N = c->N;
-    if (m) *m = c->m;
+    if (m) *m = c->dc;   // A's columns (the variable count of a multi-output context: scs_get_outputs)
     if (Ng) *Ng = c->Nglob;
     if (r0) *r0 = c->row0;
   });
@@ -3812,6 +3963,7 @@ int scs_set_sparse(scs_ctx* c, int64_t N, int64_t m, int64_t nnz, const int64_t*
                    const double* val, const int64_t* colptr, const int32_t* rowidx, const double* valT, int f32,
                    const double* y, int64_t Nglob, int64_t row0) {
   return guarded(c, [&] {
+    refuse_multi(c, "a sparse A (scs_set_sparse)");
     if (nnz < 0 || !rowptr || !colptr || (nnz > 0 && (!colidx || !val || !rowidx || !valT)))
       fail(c, SCS_ERR_ARG, "sparse A: null arrays");
     if (rowptr[0] != 0 || rowptr[N] != nnz || colptr[0] != 0 || colptr[m] != nnz)
@@ -3956,6 +4108,7 @@ int scs_set_sparse_device(scs_ctx* c, int64_t N, int64_t m, int64_t nnz, const v
                     "scs_set_sparse_device"};
   if (is_group(c)) return refuse_group_device(c, s.what);
   return guarded(c, [&] {
+    refuse_multi(c, "a sparse A (scs_set_sparse_device)");
     HCK(hipSetDevice(c->dev));
     check_sparse_src(c, s, N, m, nnz);
     const CsrBufs b = ingest_csr(c, s, N, m, nnz, f32 ? 1 : 0);
@@ -3977,6 +4130,7 @@ int scs_set_sparse_device(scs_ctx* c, int64_t N, int64_t m, int64_t nnz, const v
 int scs_gen_sparse(scs_ctx* c, const scs_synth* s, int f32) {
   return guarded(c, [&] {
     if (!s) fail(c, SCS_ERR_ARG, "null synth spec");
+    refuse_multi(c, "a sparse A (scs_gen_sparse)");
     if (s->kind != 4) fail(c, SCS_ERR_ARG, "scs_gen_sparse: kind must be 4");
     const int64_t N = s->N, m = s->m;
     if (N <= 0 || (N & (N - 1)) != 0 || m <= 0 || N % m != 0)
@@ -4067,7 +4221,7 @@ static void test_view_dims(scs_ctx* c, int64_t N, int64_t Nglob, bool sparse, bo
   v.Npad = std::max<int64_t>(round_up(std::max<int64_t>(N, 1), 16), 16);
   v.nstage = v.Npad / 16;
   v.sparse = sparse;
-  v.y = dalloc<double>(c, v.Npad);
+  v.y = dalloc<double>(c, v.Npad * kout(c));
   if (!sparse) {   // dense held-out rows follow the context's storage mode
     v.a32 = c->dense_f32;
     v.A = alloc_A(c, v.Npad, v.a32, zero_A);
@@ -4089,7 +4243,7 @@ static int set_test_any(scs_ctx* c, int64_t N, const DenseSrc& src, const double
       if (!y) fail(c, SCS_ERR_ARG, "%s: y is NULL (dA and y are both required)", src.what);
       if (!c->has_data || c->generic)
         fail(c, SCS_ERR_STATE, "test data needs a data problem: call scs_set_data / scs_gen_data / scs_set_sparse first");
-      check_device_src(c, src, N, c->m);
+      check_device_src(c, src, N, c->dc);
     }
     if (A && y) refuse_f32_quadratic(c, in32 | c->dense_f32);
     if (in32 && A) c->dense_f32 = 1;
@@ -4134,6 +4288,7 @@ int scs_set_test_sparse(scs_ctx* c, int64_t N, int64_t nnz, const int64_t* rowpt
     return SCS_ERR_ARG;
   }
   return guarded(c, [&] {
+    refuse_multi(c, "sparse held-out rows (scs_set_test_sparse)");
     HCK(hipSetDevice(c->dev));
     free_test(c);
     if (!rowptr || !y || nnz < 0 || (nnz > 0 && (!colidx || !val)))
@@ -4172,6 +4327,7 @@ int scs_set_test_sparse_device(scs_ctx* c, int64_t N, int64_t nnz, const void* d
                     "scs_set_test_sparse_device"};
   if (is_group(c)) return refuse_group_device(c, s.what);
   return guarded(c, [&] {
+    refuse_multi(c, "sparse held-out rows (scs_set_test_sparse_device)");
     HCK(hipSetDevice(c->dev));
     if (!y) fail(c, SCS_ERR_ARG, "%s: y is NULL (the CSR arrays and y are both required)", s.what);
     if (!c->has_data || c->generic)
@@ -4196,6 +4352,7 @@ int scs_gen_test_data(scs_ctx* c, const scs_synth* s) {
   if (is_group(c)) return group_gen_test_data(c, s);
   return guarded(c, [&] {
     if (!s) fail(c, SCS_ERR_ARG, "null synth spec");
+    refuse_multi(c, "scs_gen_test_data (the synthetic generator has one target column)");
     if (s->kind < 1 || s->kind > 3) fail(c, SCS_ERR_ARG, "scs_gen_test_data: dense kinds 1-3");
     if (s->m != c->m) fail(c, SCS_ERR_ARG, "scs_gen_test_data: m = %lld, the data has %lld", (long long)s->m,
                            (long long)c->m);
@@ -4256,8 +4413,21 @@ int scs_set_loss(scs_ctx* c, int loss, int ggn, double scale) {
   }
   if (is_group(c)) return group_run(c, [&](scs_ctx* s_, int) { return scs_set_loss(s_, loss, ggn, scale); });
   return guarded(c, [&] {
-    if (loss < SCS_LOSS_LOGISTIC_MARGIN || loss > SCS_LOSS_SAMPLEWISE) fail(c, SCS_ERR_ARG, "unknown loss %d", loss);
-    if (ggn < SCS_GGN_NONE || ggn > SCS_GGN_SAMPLEWISE) fail(c, SCS_ERR_ARG, "unknown ggn kind %d", ggn);
+    if (loss < SCS_LOSS_LOGISTIC_MARGIN || loss > SCS_LOSS_MULTI_LS) fail(c, SCS_ERR_ARG, "unknown loss %d", loss);
+    if (ggn < SCS_GGN_NONE || ggn > SCS_GGN_LINEAR_MULTI_LS) fail(c, SCS_ERR_ARG, "unknown ggn kind %d", ggn);
+    if (multi(c) && !multi_loss(loss)) {
+      const char* const names[] = {"", "logistic_margin", "logistic_ce", "least_squares", "quadratic", "rosenbrock",
+                                   "callback", "samplewise"};
+      fail(c, SCS_ERR_ARG, "scs_set_outputs (nout = %d) takes SCS_LOSS_SOFTMAX_CE or SCS_LOSS_MULTI_LS, not the %s loss "
+                           "(kind %d)", c->nout, names[loss], loss);
+    }
+    if (multi_loss(loss) && !multi(c))
+      fail(c, SCS_ERR_ARG, "SCS_LOSS_SOFTMAX_CE / SCS_LOSS_MULTI_LS need scs_set_outputs(nout) before the data");
+    if ((ggn == SCS_GGN_LINEAR_SOFTMAX_CE && loss != SCS_LOSS_SOFTMAX_CE) ||
+        (ggn == SCS_GGN_LINEAR_MULTI_LS && loss != SCS_LOSS_MULTI_LS) ||
+        (multi_loss(loss) && ggn != SCS_GGN_NONE && ggn != SCS_GGN_LINEAR_SOFTMAX_CE && ggn != SCS_GGN_LINEAR_MULTI_LS))
+      fail(c, SCS_ERR_ARG, "SCS_GGN_LINEAR_SOFTMAX_CE goes with SCS_LOSS_SOFTMAX_CE and SCS_GGN_LINEAR_MULTI_LS with "
+                           "SCS_LOSS_MULTI_LS (got loss %d, ggn %d)", loss, ggn);
     if ((loss == SCS_LOSS_SAMPLEWISE) != (ggn == SCS_GGN_SAMPLEWISE) && !(loss == SCS_LOSS_SAMPLEWISE && ggn == SCS_GGN_NONE))
       fail(c, SCS_ERR_ARG, "SCS_LOSS_SAMPLEWISE takes SCS_GGN_NONE or SCS_GGN_SAMPLEWISE, and no other loss takes the latter");
     if (loss == SCS_LOSS_SAMPLEWISE) {
@@ -4486,6 +4656,7 @@ int scs_method_init(scs_ctx* c, int method, int ss_type, int use_prox, int mem) 
       fail(c, SCS_ERR_ARG, "ProxGGNSCORE on a callback loss needs jac_yx / grad_fy / hess_fy (ggn_rows > 0)");
     if (method == SCS_PROX_GGNSCORE && c->loss != SCS_LOSS_CALLBACK && (c->generic || c->loss == SCS_LOSS_QUADRATIC))
       fail(c, SCS_ERR_ARG, "ProxGGNSCORE needs a data problem with an out_fn (GGN kind)");
+    refuse_multi_sample_space(c, method);
     c->method = method;
     c->ss_type = ss_type;
     c->use_prox = use_prox;
@@ -4575,6 +4746,9 @@ int scs_set_batches(scs_ctx* c, const int64_t* rows, const int64_t* offsets, int
     clear_batches(c);
     invalidate_caches(c);
     if (nbatch == 0) return;
+    if (multi(c))
+      fail(c, SCS_ERR_ARG, "scs_set_batches: minibatches (batch_size / slice_samples) are not supported with "
+                           "scs_set_outputs (nout = %d)", c->nout);
     if (!c->has_data) fail(c, SCS_ERR_STATE, "no data: call scs_set_data / scs_gen_data first");
     if (c->generic) fail(c, SCS_ERR_ARG, "a ProblemGeneric has no samples to batch");
     if (nbatch < 0 || !rows || !offsets || offsets[0] != 0) fail(c, SCS_ERR_ARG, "scs_set_batches: bad batch list");
@@ -4880,7 +5054,8 @@ int scs_iterate_ex(scs_ctx* c, const double* x0, const double* x_star, int64_t m
       const bool fused = c->method == SCS_PROX_LQNSCORE && c->ss_type == 1 && m >= 16384 && !sharded(c) &&
                          c->smooth != SCS_SMOOTH_PHUBER_GL && c->smooth != SCS_SMOOTH_OSBA_GL &&
                          !(c->use_prox && c->reg == SCS_REG_GL) && c->reg != SCS_REG_GL && !(fz && fz[0] == '0') &&
-                         c->loss != SCS_LOSS_SAMPLEWISE;   // its epoch is pipelined past the caller's functions
+                         c->loss != SCS_LOSS_SAMPLEWISE &&   // its epoch is pipelined past the caller's functions
+                         !multi(c);   // the fused epoch's post pass reads single-vector Aᵀv partials
       if (fused) {
         const double Mg = get_Mg(c, c->Mh, c->nu, c->mu, m);
         const double step = c->has_L ? jl_min_h(1 / c->L, 1.0) : 0.5;
@@ -5199,6 +5374,7 @@ int scs_prox_eval(scs_ctx* c, const double* z, const double* Hr, double lam, dou
 
 int scs_gram_eval(scs_ctx* c, const double* w, double* G, int64_t ldg) {
   return guarded(c, [&] {
+    refuse_multi(c, "scs_gram_eval (scs_multi_products_eval / scs_multi_system_eval serve it)");
     if (!c->has_data || c->generic) fail(c, SCS_ERR_STATE, "no data");
     std::vector<double> wp(c->Npad, 0.0);
     std::memcpy(wp.data(), w, sizeof(double) * c->N);
@@ -5220,6 +5396,7 @@ int scs_gram_eval(scs_ctx* c, const double* w, double* G, int64_t ldg) {
 // the nonzeros (scs_set_sparse_sample on a sparse A), else the Aᵀ copy (of the mirror) on the MFMA tiles
 int scs_sample_gram_eval(scs_ctx* c, const double* h, double* P, int64_t ldp) {
   return guarded(c, [&] {
+    refuse_multi(c, "scs_sample_gram_eval (scs_multi_products_eval / scs_multi_system_eval serve it)");
     if (!c->has_data || c->generic) fail(c, SCS_ERR_STATE, "no data");
     if (sharded(c)) fail(c, SCS_ERR_ARG, "scs_sample_gram_eval runs on one rank");
     if (!h || !P) fail(c, SCS_ERR_ARG, "scs_sample_gram_eval: null argument");
@@ -5286,6 +5463,7 @@ int scs_sample_gram_eval(scs_ctx* c, const double* h, double* P, int64_t ldp) {
 int scs_solve_eval(scs_ctx* c, const double* w, const double* dvec, const double* rhs, int mode, double* x,
                    int* used_lu) {
   return guarded(c, [&] {
+    refuse_multi(c, "scs_solve_eval (scs_multi_products_eval / scs_multi_system_eval serve it)");
     if (!c->has_data || c->generic) fail(c, SCS_ERR_STATE, "no data");
     if (c->nranks > 1) fail(c, SCS_ERR_ARG, "scs_solve_eval runs on one rank");
     if (!w || !dvec || !rhs || !x) fail(c, SCS_ERR_ARG, "scs_solve_eval: null argument");
@@ -5363,7 +5541,7 @@ int scs_get_columns(scs_ctx* c, const int64_t* cols, int64_t ncols, double* out)
   return guarded(c, [&] {
     if (!c->has_data || c->generic || c->sparse) fail(c, SCS_ERR_STATE, "scs_get_columns needs a dense A");
     for (int64_t k = 0; k < ncols; ++k)
-      if (cols[k] < 0 || cols[k] >= c->m) fail(c, SCS_ERR_ARG, "column %lld out of range", (long long)cols[k]);
+      if (cols[k] < 0 || cols[k] >= c->dc) fail(c, SCS_ERR_ARG, "column %lld out of range", (long long)cols[k]);
     HCK(hipSetDevice(c->dev));
     int64_t* dc = dalloc<int64_t>(c, ncols);
     double* dout = dalloc<double>(c, (size_t)ncols * c->N);
@@ -5381,6 +5559,7 @@ int scs_get_columns(scs_ctx* c, const int64_t* cols, int64_t ncols, double* out)
 int scs_gram_atv_eval(scs_ctx* c, const double* w, const double* v, const int64_t* ij, int64_t n, double* gvals,
                       double* atv, int* fused) {
   return guarded(c, [&] {
+    refuse_multi(c, "scs_gram_atv_eval (scs_multi_products_eval / scs_multi_system_eval serve it)");
     if (!c->has_data || c->generic) fail(c, SCS_ERR_STATE, "no data");
     if (n < 0 || (n > 0 && (!ij || !gvals))) fail(c, SCS_ERR_ARG, "scs_gram_atv_eval: bad sample list");
     HCK(hipSetDevice(c->dev));
@@ -5419,6 +5598,7 @@ int scs_gram_atv_eval(scs_ctx* c, const double* w, const double* v, const int64_
 
 int scs_gemv_t_eval(scs_ctx* c, const double* v, double* out) {
   return guarded(c, [&] {
+    refuse_multi(c, "scs_gemv_t_eval (scs_multi_products_eval / scs_multi_system_eval serve it)");
     if (!c->has_data || c->generic) fail(c, SCS_ERR_STATE, "no data");
     std::vector<double> vp(c->Npad, 0.0);
     std::memcpy(vp.data(), v, sizeof(double) * c->N);
@@ -5431,6 +5611,7 @@ int scs_gemv_t_eval(scs_ctx* c, const double* v, double* out) {
 
 int scs_gemv_n_eval(scs_ctx* c, const double* x, double* out) {
   return guarded(c, [&] {
+    refuse_multi(c, "scs_gemv_n_eval (scs_multi_products_eval / scs_multi_system_eval serve it)");
     if (!c->has_data || c->generic) fail(c, SCS_ERR_STATE, "no data");
     h2d(c, c->xn, x, c->m);
     const int ns = matvec_n(c, c->xn, c->nsplit);
@@ -5439,6 +5620,112 @@ int scs_gemv_n_eval(scs_ctx* c, const double* x, double* out) {
     d2h(c, out, c->z, c->N);
     sync(c);
     c->zvalid = false;
+  });
+}
+
+// ---- multi-output targets -------------------------------------------------------------------
+int scs_set_outputs(scs_ctx* c, int nout) {
+  if (!c) return SCS_ERR_ARG;
+  if (is_group(c)) {
+    c->err = "scs_set_outputs takes a single-device context (scs_create): a multi-device context (devices=[...]) is "
+             "not supported with nout";
+    return SCS_ERR_ARG;
+  }
+  return guarded(c, [&] {
+    if (nout != 0 && (nout < 2 || nout > 16))
+      fail(c, SCS_ERR_ARG, "scs_set_outputs: nout = %d is outside 2..16 (0 clears the mode)", nout);
+    if (nout && c->nranks > 1) fail(c, SCS_ERR_ARG, "nranks > 1 is not supported with scs_set_outputs (nout = %d)", nout);
+    if (nout == c->nout) return;
+    HCK(hipSetDevice(c->dev));
+    if (c->has_data) {   // the dimensions change meaning: the data goes, as with a new data door
+      sync(c);
+      reset_data(c);
+    }
+    c->loss_set = false;
+    c->nout = nout;
+  });
+}
+
+int scs_get_outputs(scs_ctx* c, int* nout, int64_t* nvar) {
+  if (!c) return SCS_ERR_ARG;
+  if (is_group(c)) {
+    if (nout) *nout = 1;
+    if (nvar) *nvar = c->grpm;
+    return SCS_OK;
+  }
+  return guarded(c, [&] {
+    if (nout) *nout = kout(c);
+    if (nvar) *nvar = c->m;
+  });
+}
+
+// A X (N x K) and Aᵀ V (d x K) of host operands through multi.hip's kernels; K is the call's own
+int scs_multi_products_eval(scs_ctx* c, int K, const double* X, const double* V, double* AX, double* ATV) {
+  return guarded(c, [&] {
+    if (!c->has_data || c->generic || c->sparse) fail(c, SCS_ERR_STATE, "scs_multi_products_eval needs a dense A");
+    if (K < 1 || K > 16) fail(c, SCS_ERR_ARG, "scs_multi_products_eval: K = %d is outside 1..16", K);
+    if ((X == nullptr) != (AX == nullptr) || (V == nullptr) != (ATV == nullptr))
+      fail(c, SCS_ERR_ARG, "scs_multi_products_eval: X goes with AX and V with ATV");
+    HCK(hipSetDevice(c->dev));
+    const int64_t N = c->N, Npad = c->Npad, d = c->dc, dcp = c->dcp;
+    if (X) {
+      const int ns = gemv_n_splits(Npad, d);
+      double* dX = dalloc<double>(c, (size_t)d * K);
+      double* Xt = dalloc<double>(c, (size_t)dcp * K);
+      double* part = dalloc<double>(c, (size_t)ns * K * Npad);
+      double* Z = dalloc<double>(c, (size_t)K * Npad);
+      h2d(c, dX, X, d * K);
+      HCK(launch_multi_pack_x(dX, d, dcp, K, Xt, c->st));
+      HCK(launch_multi_ax(c->A, c->a32, c->nstage, Npad, dcp, K, Xt, ns, part, c->st));
+      HCK(launch_multi_epilogue(SCS_LOSS_MULTI_LS, EPI_Z, K, part, ns, nullptr, N, Npad, 1.0, Z, nullptr, nullptr, nullptr,
+                                nullptr, c->st));
+      if (N > 0)
+        HCK(hipMemcpy2DAsync(AX, sizeof(double) * N, Z, sizeof(double) * Npad, sizeof(double) * N, K,
+                             hipMemcpyDeviceToHost, c->st));
+      sync(c);
+      for (double** q : {&dX, &Xt, &part, &Z}) dfree_t(c, *q);
+    }
+    if (V) {
+      const int nch = multi_atv_chunks(Npad);
+      double* dV = dalloc<double>(c, (size_t)Npad * K);   // zeroed: rows N..Npad stay zero
+      double* part = dalloc<double>(c, (size_t)nch * K * dcp);
+      double* out = dalloc<double>(c, (size_t)d * K);
+      if (N > 0)
+        HCK(hipMemcpy2DAsync(dV, sizeof(double) * Npad, V, sizeof(double) * N, sizeof(double) * N, K,
+                             hipMemcpyHostToDevice, c->st));
+      double* Vt = multi_vt(c, Npad * K);
+      HCK(launch_multi_pack_v(dV, Npad, Npad, K, Vt, c->st));
+      HCK(launch_multi_atv(c->A, c->a32, c->nstage, Npad, d, dcp, K, Vt, part, c->st));
+      HCK(launch_multi_atv_finalize(part, nch, K, dcp, d, out, c->st));
+      d2h(c, ATV, out, d * K);
+      sync(c);
+      for (double** q : {&dV, &part, &out}) dfree_t(c, *q);
+    }
+  });
+}
+
+// the assembled JᵀQJ (before λ diag Hr), vec(AᵀR) and f at x, by the step's own path
+int scs_multi_system_eval(scs_ctx* c, const double* x, double* G, int64_t ldg, double* g, double* f) {
+  return guarded(c, [&] {
+    if (!c->has_data || c->generic) fail(c, SCS_ERR_STATE, "no data");
+    if (!multi(c)) fail(c, SCS_ERR_STATE, "scs_multi_system_eval needs a multi-output context (scs_set_outputs)");
+    if (!c->loss_set) fail(c, SCS_ERR_STATE, "no loss: call scs_set_loss first");
+    if (!x || (G && ldg < c->m)) fail(c, SCS_ERR_ARG, "scs_multi_system_eval: null x or ldg < nvar");
+    HCK(hipSetDevice(c->dev));
+    const int64_t m = c->m;
+    invalidate_caches(c);
+    h2d(c, c->x, x, m);
+    const double fv = forward(c, x, c->x, EPI_GGN);
+    gemv_t_local(c, c->gN, c->gtmp);
+    multi_system(c);
+    if (G)
+      HCK(hipMemcpy2DAsync(G, sizeof(double) * ldg, c->G, sizeof(double) * c->mpad, sizeof(double) * m, m,
+                           hipMemcpyDeviceToHost, c->st));
+    if (g) d2h(c, g, c->gtmp, m);
+    sync(c);
+    if (f) *f = fv;
+    invalidate_caches(c);
+    if (c->timing) tresolve(c);
   });
 }
 

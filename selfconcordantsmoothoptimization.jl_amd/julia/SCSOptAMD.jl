@@ -21,8 +21,8 @@ export DeviceProblem, configure!, iterate_device!, set_gram_cache!, set_solver!,
 const lib = joinpath(@__DIR__, "..", "scsopt", "libscsopt.so")
 
 const LOSS = Dict(:logistic_margin => 1, :logistic_ce => 2, :least_squares => 3, :quadratic => 4, :rosenbrock => 5,
-                  :callback => 6)
-const GGN = Dict(nothing => 0, :sigmoid_ce => 1, :linear_ls => 2)
+                  :callback => 6, :softmax_ce => 8, :multi_least_squares => 9)
+const GGN = Dict(nothing => 0, :sigmoid_ce => 1, :linear_ls => 2, :linear_softmax_ce => 4, :linear_multi_ls => 5)
 const REG = Dict("l1" => 1, "l2" => 2, "indbox" => 3, "gl" => 4)
 const SCS_ERR_REF = 5
 const SCS_ERR_CALLBACK = 7
@@ -246,6 +246,62 @@ function DeviceProblem(A::Matrix{Float64}, y::AbstractVector, x0::Vector{Float64
               ctx, N, m, A, N, yv, N_global, row0), ctx)
     model = finish_problem(ctx, A, yv, x0, loss, λ, out_fn, scale, L, sol, C_set, P)
     return set_test!(model, Atest, ytest; Ntest_global, test_row0)
+end
+
+# A multi-output target (optim_loop! reads ny = size(model.y, 2), iterate.jl:106): Y is N x K, 2 <= K <= 16,
+# x0 = vec(X0) with X0 d x K, loss :softmax_ce (out_fn :linear_softmax_ce) or :multi_least_squares
+# (out_fn :linear_multi_ls).  scs_set_outputs goes before the data door, whose m is then A's column
+# count d; A stays on the device as one N x d block (Matrix{Float32}: stored as fp32).  One device, one
+# rank, the full batch; an Atest takes an Ntest x K ytest.
+function DeviceProblem(A::Union{Matrix{Float64},Matrix{Float32}}, Y::AbstractMatrix, x0::Vector{Float64},
+                       loss::Symbol, λ; out_fn::Union{Symbol,Nothing}=nothing, scale::Float64=1.0 / size(A, 1),
+                       L=nothing, sol::Vector{Float64}=zero(x0), C_set=nothing, P=nothing, device::Integer=0,
+                       Atest=nothing, ytest=nothing)
+    N, d = size(A)
+    K = size(Y, 2)
+    (size(Y, 1) == N && length(x0) == d * K) ||
+        throw(DimensionMismatch("Y must be N x K and length(x0) = size(A, 2) * K"))
+    ctx = create_ctx(device)
+    chk(ccall((:scs_set_outputs, lib), Cint, (Ptr{Cvoid}, Cint), ctx, K), ctx)
+    Ym = Matrix{Float64}(Y)
+    if A isa Matrix{Float32}
+        chk(ccall((:scs_set_data_f32, lib), Cint,
+                  (Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}, Int64, Ptr{Float64}, Int64, Int64),
+                  ctx, N, d, A, N, Ym, N, 0), ctx)
+    else
+        chk(ccall((:scs_set_data, lib), Cint,
+                  (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Int64),
+                  ctx, N, d, A, N, Ym, N, 0), ctx)
+    end
+    model = finish_problem(ctx, A, Ym, x0, loss, λ, out_fn, scale, L, sol, C_set, P)
+    return set_test!(model, Atest, ytest)
+end
+
+# (nout, the length of x) of a context: (1, m) without scs_set_outputs
+function get_outputs(model::DeviceProblem)
+    k = Ref{Cint}(0); nv = Ref{Int64}(0)
+    chk(ccall((:scs_get_outputs, lib), Cint, (Ptr{Cvoid}, Ref{Cint}, Ref{Int64}), model.ctx, k, nv), model.ctx)
+    return Int(k[]), Int(nv[])
+end
+
+# A*X (N x K) and A'*V (d x K) through the multi-output kernels (parity tests); 1 <= K <= 16
+function multi_products(model::DeviceProblem, X::Matrix{Float64}, V::Matrix{Float64})
+    N, K = size(V); d = size(X, 1)
+    AX = zeros(N, K); ATV = zeros(d, K)
+    chk(ccall((:scs_multi_products_eval, lib), Cint,
+              (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+              model.ctx, K, X, V, AX, ATV), model.ctx)
+    return AX, ATV
+end
+
+# (J'QJ before λ*Diagonal(Hr), vec(A'R), f) of a multi-output problem at x, by the step's own path
+function multi_system(model::DeviceProblem, x::Vector{Float64})
+    n = length(x)
+    G = zeros(n, n); g = zeros(n); f = Ref{Float64}(0.0)
+    chk(ccall((:scs_multi_system_eval, lib), Cint,
+              (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ref{Float64}),
+              model.ctx, x, G, n, g, f), model.ctx)
+    return G, g, f[]
 end
 
 # A::Matrix{Float32} (A::DataTupleOrArray2 admits it, problems.jl:61-62; with x::Vector{Float64} Julia

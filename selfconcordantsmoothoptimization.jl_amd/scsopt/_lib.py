@@ -24,8 +24,8 @@ SCS_CB_NO_METHOD = 2   # a callback's answer to SCS_CB_GRAD_X when grad_fx takes
 SCS_SW_VALUE, SCS_SW_D1, SCS_SW_D2, SCS_SW_GGN = 1, 2, 4, 8   # scs_samplewise_fn's `what` bits
 
 LOSS = {"logistic_margin": 1, "logistic_ce": 2, "least_squares": 3, "quadratic": 4, "rosenbrock": 5, "callback": 6,
-        "samplewise": 7}
-GGN = {None: 0, "sigmoid_ce": 1, "linear_ls": 2, "samplewise": 3}
+        "samplewise": 7, "softmax_ce": 8, "multi_least_squares": 9}
+GGN = {None: 0, "sigmoid_ce": 1, "linear_ls": 2, "samplewise": 3, "linear_softmax_ce": 4, "linear_multi_ls": 5}
 REG = {"l1": 1, "l2": 2, "indbox": 3, "gl": 4}
 SMOOTH = {"phuber_l1l2": 1, "phuber_indbox": 2, "phuber_gl": 3, "exp_indbox": 4, "logexp_indbox": 5, "osba_l1l2": 6,
           "osba_gl": 7}
@@ -113,6 +113,8 @@ _SIGS = {
     "scs_set_reduce_buffer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "scs_comm_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                 C.POINTER(C.c_int), C.c_char_p, C.c_int64]),
+    "scs_set_outputs": (C.c_int, [C.c_void_p, C.c_int]),
+    "scs_get_outputs": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), c_i64p]),
     "scs_set_data": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, c_dp, C.c_int64, c_dp, C.c_int64, C.c_int64]),
     "scs_gen_data": (C.c_int, [C.c_void_p, C.POINTER(Synth)]),
     "scs_set_dense_f32": (C.c_int, [C.c_void_p, C.c_int]),
@@ -181,6 +183,8 @@ _SIGS = {
     "scs_lu_eval": (C.c_int, [C.c_void_p, C.c_int64, c_dp, c_dp, c_dp, c_i32p, C.POINTER(C.c_int)]),
     "scs_get_columns": (C.c_int, [C.c_void_p, c_i64p, C.c_int64, c_dp]),
     "scs_gram_atv_eval": (C.c_int, [C.c_void_p, c_dp, c_dp, c_i64p, C.c_int64, c_dp, c_dp, C.POINTER(C.c_int)]),
+    "scs_multi_products_eval": (C.c_int, [C.c_void_p, C.c_int, c_dp, c_dp, c_dp, c_dp]),
+    "scs_multi_system_eval": (C.c_int, [C.c_void_p, c_dp, c_dp, C.c_int64, c_dp, c_dp]),
     "scs_timing_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "scs_timing_get": (C.c_int, [C.c_void_p, C.POINTER(Timing)]),
     "scs_timing_reset": (C.c_int, [C.c_void_p]),
@@ -274,6 +278,22 @@ def parse_device_matrix(iface):
         raise ValueError("__cuda_array_interface__ forbids stream = 0 (1 and 2 name the default streams)")
     return {"ptr": int(ptr) if ptr else 0, "N": N, "m": m, "elem_bytes": es, "stride_n": sn, "stride_m": sm,
             "stream": None if stream is None else int(stream)}
+
+
+def parse_device_targets(iface, n, k):
+    """A device Y of a multi-output problem: n x k float64, column-major with leading dimension n (a
+    Fortran-ordered array, or the transpose of a C-contiguous k x n one) -> its pointer."""
+    if iface["typestr"] != "<f8":
+        raise TypeError(f"a device Y must be float64, got {iface['typestr']!r}")
+    shape = tuple(int(v) for v in iface["shape"])
+    if shape != (n, k):
+        raise ValueError(f"Y has shape {shape}, expected ({n}, {k})")
+    strides = iface.get("strides")
+    st = (8 * k, 8) if strides is None else tuple(int(b) for b in strides)
+    if not ((n == 1 or st[0] == 8) and (k == 1 or st[1] == 8 * n)):
+        raise ValueError(f"a device Y must be column-major with leading dimension N (strides (8, {8 * n}) bytes), got "
+                         f"{st}: pass Y.t().contiguous().t() / cupy.asfortranarray(Y); it is not copied here")
+    return int(iface["data"][0] or 0)
 
 
 def parse_device_vector(iface, n):

@@ -131,6 +131,52 @@ def samplewise(value, d1=None, d2=None, *, link=None, link_d1=None, grad_fy=None
     return SamplewiseLoss("samplewise", 1.0, value, d1, d2, link, link_d1, grad_fy, hess_fy, bool(device))
 
 
+@dataclass(frozen=True)
+class MultiLoss(Loss):
+    """A loss with nout = K outputs on one A: x = vec(X), X d x K column-major; Y is N x K."""
+    nout: int = 2
+
+    def __repr__(self):
+        return f"{self.kind}(nout={self.nout}, scale={self.scale!r})"
+
+
+@dataclass(frozen=True)
+class MultiOutFn(OutFn):
+    """out_fn(A, x) = A*X of a multi-output loss with its ŷ-form f(Y, ŷ) (ProxGGNSCORE)."""
+    nout: int = 2
+
+
+def _check_nout(nout):
+    k = int(nout)
+    if k != nout or not 2 <= k <= 16:
+        raise ValueError(f"nout = {nout!r} is outside 2..16")
+    return k
+
+
+def softmax_ce(nout: int, scale: float = 1.0) -> MultiLoss:
+    """Multinomial logistic regression on the device: x = vec(X), X d x nout (entry (j, l) at j + d*l),
+    Z = A*X, P = softmax of the rows of Z, f(A, Y, x) = -scale*sum(Y .* log.(P)) with Y N x nout (rows
+    need not be one-hot).  ∇f = vec(Aᵀ R), R = scale*(s_i P - Y), s_i = Σ_k Y_ik; block (k, l) of the
+    Hessian is Aᵀ diag(scale s_i (δ_kl P_ik - P_ik P_il)) A.  A stays on the device as one N x d block."""
+    return MultiLoss("softmax_ce", float(scale), _check_nout(nout))
+
+
+def multi_least_squares(nout: int, scale: float = 1.0) -> MultiLoss:
+    """f(A, Y, x) = 0.5*scale*sum((A*X .- Y).^2), X = reshape(x, d, nout), Y N x nout."""
+    return MultiLoss("multi_least_squares", float(scale), _check_nout(nout))
+
+
+def linear_softmax_ce(nout: int, scale: float = 1.0) -> MultiOutFn:
+    """out_fn(A, x) = A*X (the logits) with f(Y, ŷ) = -scale*sum(Y .* log.(softmax(ŷ))): J = I ⊗ A and
+    Q is block-diagonal per sample, scale s_i (diag(P_i) - P_i P_iᵀ)."""
+    return MultiOutFn("linear_softmax_ce", float(scale), _check_nout(nout))
+
+
+def linear_multi_ls(nout: int, scale: float = 1.0) -> MultiOutFn:
+    """out_fn(A, x) = A*X with f(Y, ŷ) = 0.5*scale*sum((ŷ .- Y).^2): J = I ⊗ A, Q = scale*I."""
+    return MultiOutFn("linear_multi_ls", float(scale), _check_nout(nout))
+
+
 def sigmoid_ce(scale: float = 1.0) -> OutFn:
     """Mfunc(A,x) = 1 ./ (1 .+ exp.(-A*x)) with f(y,ŷ) = -scale*sum(y.*log.(ŷ) .+ (1 .- y).*log.(1 .- ŷ))
     (test/test_algs.jl:10-11, README.md:135-139)."""

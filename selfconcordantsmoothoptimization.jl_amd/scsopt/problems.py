@@ -118,6 +118,10 @@ class Problem:
         self.name = name
         self.comm = comm
         self.generic = A is None and _ctx is None
+        # multi-output losses (losses.softmax_ce / multi_least_squares): K = nout outputs on one N x d A,
+        # x = vec(X) with X d x K, Y N x K (scs_set_outputs)
+        self.nout = self._check_outputs(f, out_fn, A, comm, devices, _ctx)
+        self.d = self.m // self.nout   # A's columns
         if f.kind == "callback":   # the data stays with the caller's closures; the device holds none
             if _ctx is not None or comm is not None:
                 raise ValueError("a callback loss runs on one rank with host-side data")
@@ -140,6 +144,8 @@ class Problem:
             self.ctx.check(_lib.lib.scs_set_sparse_batches(self.ctx.h, 1))
         if sparse_sample:
             self.ctx.check(_lib.lib.scs_set_sparse_sample(self.ctx.h, 1))
+        if self.nout > 1:   # before the data door: its m is then A's column count d, y is N x nout
+            self.ctx.check(_lib.lib.scs_set_outputs(self.ctx.h, self.nout))
         if comm is not None and comm.active and _ctx is None:
             comm.attach(self.ctx)
         if _ctx is None:
@@ -152,6 +158,8 @@ class Problem:
                 self._set_sparse(A, y, N_global, row0, f32=bool(sparse_f32))
             elif _lib.is_device_array(A):
                 self.N = self._set_device(A, y, False, N_global, row0)
+            elif self.nout > 1:
+                self.N = self._set_host_multi(A, y, False)
             else:
                 # a float32 matrix goes to the device as it is only with dense_f32; the default widens it
                 as32 = self.dense_f32 and isinstance(A, np.ndarray) and A.dtype == np.float32
@@ -237,6 +245,8 @@ class Problem:
             self.ctx.check(_lib.lib.scs_set_test_callback(self.ctx.h, 1))
             self.test_model = True
             return
+        if self.nout > 1 and _lib.is_device_csr(Atest):
+            raise ValueError("a sparse Atest is not supported with nout (multi-output losses take dense rows)")
         if _lib.is_device_csr(Atest):
             if len(self.ctx.devices) > 1:
                 raise ValueError("a devices=[...] problem takes host held-out rows, not a device CSR")
@@ -247,6 +257,12 @@ class Problem:
             if len(self.ctx.devices) > 1:
                 raise ValueError("a devices=[...] problem takes host held-out rows, not a device array")
             self._set_device(Atest, ytest, True, Ntest_global, row0)
+            self.test_model = True
+            return
+        if self.nout > 1:
+            if _is_sparse(Atest):
+                raise ValueError("a sparse Atest is not supported with nout (multi-output losses take dense rows)")
+            self._set_host_multi(Atest, ytest, True)
             self.test_model = True
             return
         yv = np.ascontiguousarray(np.asarray(ytest, dtype=np.float64).reshape(-1))
@@ -277,6 +293,67 @@ class Problem:
                                                           int(At.shape[0]), dptr(yv), Ng, int(row0)))
         self.test_model = True
 
+    def _check_outputs(self, f, out_fn, A, comm, devices, _ctx):
+        """nout of a multi-output problem (1 otherwise) after the refusals of scs_set_outputs, each
+        naming the option it refuses."""
+        k = getattr(f, "nout", None)
+        ko = getattr(out_fn, "nout", None)
+        if k is None and ko is None:
+            return 1
+        if k is None:
+            raise ValueError(f"out_fn {out_fn.kind}(nout={ko}) needs a multi-output loss (losses.softmax_ce / "
+                             f"losses.multi_least_squares): the {f.kind} loss is not supported with nout")
+        pair = {"softmax_ce": "linear_softmax_ce", "multi_least_squares": "linear_multi_ls"}[f.kind]
+        if out_fn is not None and (out_fn.kind != pair or ko != k):
+            raise ValueError(f"{f.kind}(nout={k}) takes out_fn = losses.{pair}({k}, scale)")
+        if not 2 <= k <= 16:
+            raise ValueError(f"nout = {k} is outside 2..16")
+        if A is None or _ctx is not None:
+            raise ValueError("a multi-output loss (nout) needs a dense A: Problem(A, Y, x0, f, λ)")
+        if _lib.is_device_csr(A) or _is_sparse(A):
+            raise ValueError("a sparse A is not supported with nout (multi-output losses take a dense A)")
+        if devices is not None:
+            raise ValueError("devices=[...] is not supported with nout (multi-output losses run on one device)")
+        if comm is not None and comm.active:
+            raise ValueError("nranks > 1 (comm) is not supported with nout (multi-output losses run on one rank)")
+        if self.m % k:
+            raise ValueError(f"len(x0) = {self.m} is not A.shape[1] * nout (nout = {k}): x = vec(X), X d x nout")
+        return int(k)
+
+    def _targets(self, Y, N):
+        """Y of a multi-output problem as what the data doors take: N x nout, column-major."""
+        if _lib.is_device_array(Y):
+            return _lib.parse_device_targets(Y.__cuda_array_interface__, N, self.nout), None
+        Yf = np.asfortranarray(np.asarray(Y, dtype=np.float64))
+        if Yf.shape != (N, self.nout):
+            raise ValueError(f"Y must be N x nout = ({N}, {self.nout}), got {Yf.shape}")
+        return Yf.ctypes.data, Yf
+
+    def _set_host_multi(self, A, Y, test):
+        """Host rows of a multi-output problem: A N x d with d * nout = len(x0), Y N x nout."""
+        as32 = self.dense_f32 and isinstance(A, np.ndarray) and A.dtype == np.float32
+        A = np.asarray(A, dtype=np.float32 if as32 else np.float64)
+        if A.ndim != 2 or A.shape[1] * self.nout != self.m:
+            raise ValueError(f"A must be N x d with d * nout = length(x0) = {self.m} (nout = {self.nout})")
+        N = int(A.shape[0])
+        Af = np.asfortranarray(A)
+        yp, _keep = self._targets(Y, N)
+        yp = C.cast(yp, _lib.c_dp)
+        h = self.ctx.h
+        if self.dense_f32 and not as32:
+            self.ctx.check(_lib.lib.scs_set_dense_f32(h, 1))
+        if test:
+            if as32:
+                rc = _lib.lib.scs_set_test_data_f32(h, N, Af.ctypes.data_as(C.c_void_p), N, yp, 0, 0)
+            else:
+                rc = _lib.lib.scs_set_test_data(h, N, Af.ctypes.data_as(_lib.c_dp), N, yp, 0, 0)
+        elif as32:
+            rc = _lib.lib.scs_set_data_f32(h, N, self.d, Af.ctypes.data_as(C.c_void_p), N, yp, N, 0)
+        else:
+            rc = _lib.lib.scs_set_data(h, N, self.d, Af.ctypes.data_as(_lib.c_dp), N, yp, N, 0)
+        self.ctx.check(rc)
+        return N
+
     def _set_device(self, A, y, test, N_global, row0):
         """A (and possibly y) already on the GPU, through __cuda_array_interface__ (a torch-ROCm tensor, a
         CuPy array): scs_set_data_device / scs_set_test_data_device re-tile it on the device, no host
@@ -284,8 +361,9 @@ class Problem:
         arrays (float32 kept only with dense_f32=True, float64 rounded on the device with it).
         Returns N."""
         d = _lib.parse_device_matrix(A.__cuda_array_interface__)
-        if d["m"] != self.m:
-            raise ValueError(f"A must be N x m with m = length(x0) = {self.m}")
+        if d["m"] * self.nout != self.m:
+            raise ValueError(f"A must be N x m with m = length(x0) = {self.m}" if self.nout == 1 else
+                             f"A must be N x d with d * nout = length(x0) = {self.m} (nout = {self.nout})")
         N = d["N"]
         yp, stream, _keep = self._device_y_and_stream((A,), y, N, d["stream"])
         if self.dense_f32:
@@ -295,7 +373,7 @@ class Problem:
             rc = _lib.lib.scs_set_test_data_device(self.ctx.h, N, d["ptr"], d["elem_bytes"], d["stride_n"],
                                                    d["stride_m"], yp, stream, Ng, int(row0))
         else:
-            rc = _lib.lib.scs_set_data_device(self.ctx.h, N, self.m, d["ptr"], d["elem_bytes"], d["stride_n"],
+            rc = _lib.lib.scs_set_data_device(self.ctx.h, N, self.d, d["ptr"], d["elem_bytes"], d["stride_n"],
                                               d["stride_m"], yp, stream, Ng if Ng else N, int(row0))
         self.ctx.check(rc)
         return N
@@ -309,7 +387,10 @@ class Problem:
             if type(a).__module__.split(".")[0] == "torch":
                 _lib.require_torch_runtime("a torch tensor as A / y")   # a second runtime's pointer is not ours
                 torch_stream = sys.modules["torch"].cuda.current_stream(a.device)
-        if _lib.is_device_array(y):
+        if self.nout > 1:   # N x nout targets, host or device
+            yp, yv = self._targets(y, N)
+            ystream = y.__cuda_array_interface__.get("stream") if yv is None else None
+        elif _lib.is_device_array(y):
             yi = y.__cuda_array_interface__
             yp, yv = _lib.parse_device_vector(yi, N), None
             ystream = yi.get("stream")
@@ -627,9 +708,11 @@ class Problem:
 
     def get_data(self, r0=0, nr=None):
         nr = self.N - r0 if nr is None else nr
-        A = np.zeros((self.m, nr), dtype=np.float64)   # column-major view: A.T is N x m
-        y = np.zeros(nr, dtype=np.float64)
+        A = np.zeros((self.d, nr), dtype=np.float64)   # column-major view: A.T is N x m
+        y = np.zeros(nr * self.nout, dtype=np.float64)   # (multi-output: nr x nout, column-major)
         self.ctx.check(_lib.lib.scs_get_data(self.ctx.h, r0, nr, dptr(A), nr, dptr(y)))
+        if self.nout > 1:
+            return np.ascontiguousarray(A.T), np.ascontiguousarray(y.reshape(self.nout, nr).T)
         return np.ascontiguousarray(A.T), y
 
     def data_info(self):
@@ -809,6 +892,37 @@ class Problem:
         self.ctx.check(_lib.lib.scs_solve_eval(self.ctx.h, dptr(w), dptr(dvec), dptr(rhs), int(mode), dptr(x),
                                                C.byref(used)))
         return x, bool(used.value)
+
+    def multi_products(self, X=None, V=None):
+        """A X (N x K) and Aᵀ V (d x K) through the multi-output kernels (scs_multi_products_eval); X is
+        d x K, V is N x K, 1 <= K <= 16 (K need not be the problem's nout).  Returns (AX, ATV), None for
+        an operand not given."""
+        K = (X if X is not None else V).shape[1]
+        ax = atv = Xf = Vf = None
+        if X is not None:
+            Xf = np.asfortranarray(np.asarray(X, dtype=np.float64))
+            if Xf.shape != (self.d, K):
+                raise ValueError(f"X must be d x K = ({self.d}, {K})")
+            ax = np.zeros((self.N, K), order="F")
+        if V is not None:
+            Vf = np.asfortranarray(np.asarray(V, dtype=np.float64))
+            if Vf.shape != (self.N, K):
+                raise ValueError(f"V must be N x K = ({self.N}, {K})")
+            atv = np.zeros((self.d, K), order="F")
+        p = lambda a: None if a is None else C.cast(a.ctypes.data, _lib.c_dp)   # noqa: E731
+        self.ctx.check(_lib.lib.scs_multi_products_eval(self.ctx.h, int(K), p(Xf), p(Vf), p(ax), p(atv)))
+        return ax, atv
+
+    def multi_system(self, x):
+        """(JᵀQJ before λ diag Hr, vec(AᵀR), f) of a multi-output problem at x, by the step's own path
+        (scs_multi_system_eval)."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        G = np.zeros((self.m, self.m), order="F")
+        g = np.empty(self.m)
+        f = C.c_double()
+        self.ctx.check(_lib.lib.scs_multi_system_eval(self.ctx.h, dptr(x), C.cast(G.ctypes.data, _lib.c_dp), self.m,
+                                                      dptr(g), C.byref(f)))
+        return G, g, f.value
 
     def get_columns(self, cols):
         """Columns of the local A (N x len(cols), float64)."""
