@@ -622,6 +622,24 @@ int scs_solve_eval(scs_ctx* ctx, const double* w, const double* dvec, const doub
  * Needs a context only.                                                                    */
 int scs_lu_eval(scs_ctx* ctx, int64_t n, const double* A, const double* b, double* x, int32_t* ipiv,
                 int* info);
+/* Test door: M x = b for a symmetric positive definite M by the hand-written Cholesky (LAPACK potrf +
+ * potrs, uplo 'U') on buffers of its own, through the sequence a step runs on its Gram (the factor
+ * with its redo after a late chain wait, the one-launch solves with their per-block redo; every
+ * SCS_CHOL_* / SCS_SOLVE_* switch read per call; scs_fallback_counts).  M: column-major n x n, only
+ * its upper triangle is read; padded to a multiple of 128 with a unit diagonal.  U (optional):
+ * column-major n x n, its upper triangle receives the factor M = UᵀU and its strict lower triangle is
+ * unspecified.  info: the first non-positive pivot (1-based, dpotrf's info; x is then not written).
+ * Needs a context only.                                                                     */
+int scs_chol_eval(scs_ctx* ctx, int64_t n, const double* M, const double* b, double* x, double* U,
+                  int* info);
+/* Test door: A x = b by the Householder QR (LAPACK geqrf conventions: beta = -sign(alpha)·‖·‖,
+ * R(c, c) = beta, tau = 0 for a column that is already zero below the diagonal) on buffers of its
+ * own, through the sequence of the sample-space system qr(I + A) \ residual (identity padding to a
+ * multiple of 128, cooperative panels with their redo, the one-launch backward solve with its
+ * per-block redo; every SCS_QR_* switch read per call; scs_fallback_counts).  A: row-major n x n.
+ * R (optional): column-major n x n, its upper triangle receives R; the strict lower triangle is
+ * unspecified (the reflectors' storage).  Needs a context only.                              */
+int scs_qr_eval(scs_ctx* ctx, int64_t n, const double* A, const double* b, double* x, double* R);
 /* Columns cols[0..ncols) of the local (dense) A, column-major N x ncols.                 */
 int scs_get_columns(scs_ctx* ctx, const int64_t* cols, int64_t ncols, double* out);
 /* The production Gram launch for weights w, with Aᵀv formed in the same pass where a step

@@ -334,6 +334,18 @@ struct scs_ctx {
   double* lub = nullptr;
   int* luinfo = nullptr;
   int64_t lu_np = 0;
+  // scs_chol_eval's own system, factor workspace and right-hand side (what G, W, ysol, trilist, rbk,
+  // cinfo and caux are to a step), sized for the padded order ce_np
+  double *ceG = nullptr, *ceW = nullptr, *cey = nullptr, *cerbk = nullptr, *ceb = nullptr;
+  int2* cetri = nullptr;
+  int* ceinfo = nullptr;
+  CholAux ceaux;
+  int64_t ce_np = 0;
+  // scs_qr_eval's: the row-major staging, the column-major system, the right-hand side, the redo copy
+  // and the QR workspace (what Ms, qrM, bS, qbk and qr are to a sample-space step)
+  double *qeS = nullptr, *qeA = nullptr, *qeb = nullptr, *qebk = nullptr;
+  QRAux qre;
+  int64_t qe_np = 0, qebk_n = 0;
   // GGN sample-space branch (N + 1 <= m): Aᵀ copy, sample Gram, (N+1)² system
   double *At = nullptr, *Ps = nullptr, *Ms = nullptr, *bS = nullptr, *uN = nullptr, *hvec = nullptr, *hg = nullptr;
   int64_t NpS = 0;
@@ -1997,21 +2009,65 @@ int lu_factor_checked(scs_ctx* c, double* M, int64_t ld, int64_t n, int64_t npad
 // that gave up (~30 s, never expected: a block waits only on blocks dispatched before it) sets caux.serr
 // and leaves rhs undefined; the solve is redone from the saved right-hand side by the per-block launches
 // (SCS_SOLVE_PERSIST=0's form)
-void chol_solve_checked(scs_ctx* c, double* rhs) {
-  const int64_t ld = c->mpad;
-  HCK(hipMemcpyAsync(c->rbk, rhs, sizeof(double) * ld, hipMemcpyDeviceToDevice, c->st));
-  HCK(chol_solve(c->G, ld, ld, c->W, rhs, c->ysol, &c->caux, c->st));
+// (CholSys: the buffers one Cholesky solve works on -- a step's own, step_chol, or scs_chol_eval's)
+struct CholSys {
+  double* G;             // the upper system, column-major ld x ld, factored in place
+  int64_t m, ld;         // order and padded order
+  double* W;             // [ld/128][128*128] inverted diagonal blocks
+  CholAux* aux;
+  const int2* trilist;   // row-major lower tiles of ld/128 blocks
+  double* ysol;          // (ld) triangular-solve scratch
+  double* rbk;           // (ld) the right-hand side before a one-launch solve
+  int* info;             // device info word
+};
+static CholSys step_chol(scs_ctx* c) {
+  return {c->G, c->m, c->mpad, c->W, &c->caux, c->trilist, c->ysol, c->rbk, c->cinfo};
+}
+
+void chol_solve_checked(scs_ctx* c, const CholSys& s, double* rhs) {
+  const int64_t ld = s.ld;
+  HCK(hipMemcpyAsync(s.rbk, rhs, sizeof(double) * ld, hipMemcpyDeviceToDevice, c->st));
+  HCK(chol_solve(s.G, ld, ld, s.W, rhs, s.ysol, s.aux, c->st));
   int late = 0;
-  if (c->caux.serr) HCK(hipMemcpyAsync(&late, c->caux.serr, sizeof(int), hipMemcpyDeviceToHost, c->st));
+  if (s.aux->serr) HCK(hipMemcpyAsync(&late, s.aux->serr, sizeof(int), hipMemcpyDeviceToHost, c->st));
   sync(c);
   if (!late && !fault_late(1)) return;
-  if (c->caux.serr) HCK(hipMemsetAsync(c->caux.serr, 0, sizeof(int), c->st));
+  if (s.aux->serr) HCK(hipMemsetAsync(s.aux->serr, 0, sizeof(int), c->st));
   ++c->fb[SCS_FB_SOLVE_BLOCKS];
-  HCK(hipMemcpyAsync(rhs, c->rbk, sizeof(double) * ld, hipMemcpyDeviceToDevice, c->st));
-  c->caux.no_persist = true;
-  const hipError_t e = chol_solve(c->G, ld, ld, c->W, rhs, c->ysol, &c->caux, c->st);
-  c->caux.no_persist = false;
+  HCK(hipMemcpyAsync(rhs, s.rbk, sizeof(double) * ld, hipMemcpyDeviceToDevice, c->st));
+  s.aux->no_persist = true;
+  const hipError_t e = chol_solve(s.G, ld, ld, s.W, rhs, s.ysol, s.aux, c->st);
+  s.aux->no_persist = false;
   HCK(e);
+}
+
+// chol_factor(s.G) with the chain launches' fallback: a dependency wait that gave up (~30 s: never
+// expected) leaves the factor incomplete, so `restore` puts the system back and the factor is redone
+// with one launch per operation (r06; was SCS_ERR_HIP).  Returns the factorization's info (0, or the
+// first non-positive pivot, 1-based).
+template <class F>
+int chol_factor_checked(scs_ctx* c, const CholSys& s, F&& restore) {
+  int info = 0;
+  HCK(hipMemsetAsync(s.info, 0, sizeof(int), c->st));
+  s.aux->chain_mode = c->rccl ? 2 : 0;   // RCCL's streams in the process: keep the factor's two apart
+  HCK(chol_factor(s.G, s.ld, s.m, s.ld, s.W, s.aux, s.trilist, s.info, c->st));
+  HCK(hipMemcpyAsync(&info, s.info, sizeof(int), hipMemcpyDeviceToHost, c->st));
+  int late = 0;   // a dependency wait of the chain launches gave up (~30 s): never expected
+  HCK(hipMemcpyAsync(&late, s.aux->serr, sizeof(int), hipMemcpyDeviceToHost, c->st));
+  sync(c);
+  if (late || (fault_late(4) && chol_dag_active(s.aux))) {
+    HCK(hipMemsetAsync(s.aux->serr, 0, sizeof(int), c->st));
+    ++c->fb[SCS_FB_CHAIN_REDO];
+    restore();
+    HCK(hipMemsetAsync(s.info, 0, sizeof(int), c->st));
+    s.aux->no_dag = true;
+    const hipError_t e = chol_factor(s.G, s.ld, s.m, s.ld, s.W, s.aux, s.trilist, s.info, c->st);
+    s.aux->no_dag = false;
+    HCK(e);
+    HCK(hipMemcpyAsync(&info, s.info, sizeof(int), hipMemcpyDeviceToHost, c->st));
+    sync(c);
+  }
+  return info;
 }
 
 // the LU fallback: the full symmetric system from the copy Gc (rebuilt from the cached Gram when
@@ -2065,42 +2121,43 @@ void solve_lu_fallback(scs_ctx* c, double* rhs, hipEvent_t e0) {
 // r06: the panels as cooperative launches (qr.hip qr_panel_coop_kernel) -- a refused launch runs that panel
 // by column steps inside qr_solve; a sweep that gave up (cinfo = -1: a workgroup never became resident)
 // leaves A and b undefined, so the solve is redone from the saved copy with the per-column launches
-static void qr_run(scs_ctx* c, double* A, int64_t npad, double* b) {
+// (q, bk, bk_n: the workspace and the redo copy -- a step's own, c->qr and c->qbk, or scs_qr_eval's)
+static void qr_run(scs_ctx* c, QRAux* q, double*& bk, int64_t& bk_n, double* A, int64_t npad, double* b) {
   const bool coop = qr_coop_wanted(npad);
   const size_t nA = (size_t)npad * npad;
   if (coop) {
-    if (c->qbk_n != npad) {
-      dfree_t(c, c->qbk);
-      c->qbk = dalloc<double>(c, nA + (size_t)npad);
-      c->qbk_n = npad;
+    if (bk_n != npad) {
+      dfree_t(c, bk);
+      bk = dalloc<double>(c, nA + (size_t)npad);
+      bk_n = npad;
     }
-    HCK(hipMemcpyAsync(c->qbk, A, sizeof(double) * nA, hipMemcpyDeviceToDevice, c->st));
-    HCK(hipMemcpyAsync(c->qbk + nA, b, sizeof(double) * npad, hipMemcpyDeviceToDevice, c->st));
+    HCK(hipMemcpyAsync(bk, A, sizeof(double) * nA, hipMemcpyDeviceToDevice, c->st));
+    HCK(hipMemcpyAsync(bk + nA, b, sizeof(double) * npad, hipMemcpyDeviceToDevice, c->st));
   }
-  const int64_t refused0 = c->qr.coop_refused;
-  HCK(qr_solve(A, npad, npad, &c->qr, b, c->st));
+  const int64_t refused0 = q->coop_refused;
+  HCK(qr_solve(A, npad, npad, q, b, c->st));
   int late = 0, cinfo = 0;
-  HCK(hipMemcpyAsync(&late, c->qr.err, sizeof(int), hipMemcpyDeviceToHost, c->st));
-  if (coop) HCK(hipMemcpyAsync(&cinfo, c->qr.cinfo, sizeof(int), hipMemcpyDeviceToHost, c->st));
+  HCK(hipMemcpyAsync(&late, q->err, sizeof(int), hipMemcpyDeviceToHost, c->st));
+  if (coop) HCK(hipMemcpyAsync(&cinfo, q->cinfo, sizeof(int), hipMemcpyDeviceToHost, c->st));
   sync(c);
-  c->fb[SCS_FB_QR_COOP_REFUSED] += c->qr.coop_refused - refused0;
+  c->fb[SCS_FB_QR_COOP_REFUSED] += q->coop_refused - refused0;
   if (cinfo == -1) {
     ++c->fb[SCS_FB_QR_COOP_REDO];
-    HCK(hipMemcpyAsync(A, c->qbk, sizeof(double) * nA, hipMemcpyDeviceToDevice, c->st));
-    HCK(hipMemcpyAsync(b, c->qbk + nA, sizeof(double) * npad, hipMemcpyDeviceToDevice, c->st));
-    c->qr.no_coop = true;
-    const hipError_t e = qr_solve(A, npad, npad, &c->qr, b, c->st);
-    c->qr.no_coop = false;
+    HCK(hipMemcpyAsync(A, bk, sizeof(double) * nA, hipMemcpyDeviceToDevice, c->st));
+    HCK(hipMemcpyAsync(b, bk + nA, sizeof(double) * npad, hipMemcpyDeviceToDevice, c->st));
+    q->no_coop = true;
+    const hipError_t e = qr_solve(A, npad, npad, q, b, c->st);
+    q->no_coop = false;
     HCK(e);
-    HCK(hipMemcpyAsync(&late, c->qr.err, sizeof(int), hipMemcpyDeviceToHost, c->st));
+    HCK(hipMemcpyAsync(&late, q->err, sizeof(int), hipMemcpyDeviceToHost, c->st));
     sync(c);
   }
   if (late || fault_late(2)) {
     // R is complete and qr.Ym still holds Qᵀb (the one-launch kernel only reads it): the backward
     // solve again by the per-block launches
-    HCK(hipMemsetAsync(c->qr.err, 0, sizeof(int), c->st));
+    HCK(hipMemsetAsync(q->err, 0, sizeof(int), c->st));
     ++c->fb[SCS_FB_QR_BLOCKS];
-    HCK(chol_back_blocks(A, npad, npad, c->qr.W, c->qr.Ym, b, c->st));
+    HCK(chol_back_blocks(A, npad, npad, q->W, q->Ym, b, c->st));
   }
 }
 
@@ -2123,7 +2180,7 @@ void solve_qr(scs_ctx* c, double* rhs, hipEvent_t e0) {
     return;
   }
   HCK(qr_prepare(c->Gc, ld, m, ld, c->st));
-  qr_run(c, c->Gc, ld, rhs);
+  qr_run(c, &c->qr, c->qbk, c->qbk_n, c->Gc, ld, rhs);
   tend(c, T_SOLVE, e0);
 }
 
@@ -2144,34 +2201,18 @@ void solve_system(scs_ctx* c, double* rhs, bool force_lu = false, bool force_qr 
   }
   int info = 0;
   if (!force_lu) {
-    HCK(hipMemsetAsync(c->cinfo, 0, sizeof(int), c->st));
-    c->caux.chain_mode = c->rccl ? 2 : 0;   // RCCL's streams in the process: keep the factor's two apart
-    HCK(chol_factor(c->G, ld, m, ld, c->W, &c->caux, c->trilist, c->cinfo, c->st));
-    HCK(hipMemcpyAsync(&info, c->cinfo, sizeof(int), hipMemcpyDeviceToHost, c->st));
-    int late = 0;   // a dependency wait of the chain launches gave up (~30 s): never expected
-    HCK(hipMemcpyAsync(&late, c->caux.serr, sizeof(int), hipMemcpyDeviceToHost, c->st));
-    sync(c);
-    if (late || (fault_late(4) && chol_dag_active(&c->caux))) {
-      // the factor is incomplete: the system again (Gc, or the cached Gram + λ diag Hr), and the
-      // factor redone with one launch per operation (r06; was SCS_ERR_HIP)
-      HCK(hipMemsetAsync(c->caux.serr, 0, sizeof(int), c->st));
-      ++c->fb[SCS_FB_CHAIN_REDO];
+    const CholSys s = step_chol(c);
+    // a redo's system: Gc, or the cached Gram + λ diag Hr
+    info = chol_factor_checked(c, s, [&] {
       if (c->g_from_cache) {
         HCK(hipMemcpyAsync(c->G, c->Gk, sizeof(double) * ld * ld, hipMemcpyDeviceToDevice, c->st));
         HCK(launch_diag_add(c->G, c->mpad, m, c->lam, c->Hr, c->st));
       } else {
         HCK(hipMemcpyAsync(c->G, c->Gc, sizeof(double) * ld * ld, hipMemcpyDeviceToDevice, c->st));
       }
-      HCK(hipMemsetAsync(c->cinfo, 0, sizeof(int), c->st));
-      c->caux.no_dag = true;
-      const hipError_t e = chol_factor(c->G, ld, m, ld, c->W, &c->caux, c->trilist, c->cinfo, c->st);
-      c->caux.no_dag = false;
-      HCK(e);
-      HCK(hipMemcpyAsync(&info, c->cinfo, sizeof(int), hipMemcpyDeviceToHost, c->st));
-      sync(c);
-    }
+    });
     if (info == 0) {
-      chol_solve_checked(c, rhs);
+      chol_solve_checked(c, s, rhs);
       solve_flag_copy(c);
       c->lu_fallback_used = false;
       tend(c, T_SOLVE, e0);
@@ -2197,7 +2238,7 @@ bool solve_factored(scs_ctx* c, double* rhs, hipEvent_t e0) {
     return false;
   }
   if (info == 0) {
-    chol_solve_checked(c, rhs);
+    chol_solve_checked(c, step_chol(c), rhs);
     solve_flag_copy(c);
     c->lu_fallback_used = false;
     tend(c, T_SOLVE, e0);
@@ -2820,7 +2861,7 @@ void ggn_sample_direction(scs_ctx* c, const double* xh) {
       c->qrM_n = np1;
     }
     HCK(qr_from_rowmajor(Ms, np1, c->qrM, np1, n1, np1, c->st));
-    qr_run(c, c->qrM, np1, bS);
+    qr_run(c, &c->qr, c->qbk, c->qbk_n, c->qrM, np1, bS);
   } else {
     HCK(lu_aux_init(&c->lu, np1, c->st));
     info = lu_factor_checked(c, Ms, np1, n1, np1, c->cinfo, [&] {   // the system assembled again
@@ -3273,6 +3314,8 @@ int scs_destroy(scs_ctx* c) {
     if (e.h) (void)hipHostFree(e.h);
   lu_aux_free(&c->lu);
   qr_aux_free(&c->qr);
+  qr_aux_free(&c->qre);
+  chol_aux_free(&c->ceaux);
   if (c->sf) {
     (void)hipStreamSynchronize(c->sf);
     (void)hipStreamDestroy(c->sf);
@@ -5532,6 +5575,92 @@ int scs_lu_eval(scs_ctx* c, int64_t n, const double* A, const double* b, double*
     if (ipiv) HCK(hipMemcpyAsync(ipiv, c->lu.ipiv, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->st));
     sync(c);
     if (info) *info = hinfo;
+    if (c->timing) tresolve(c);
+  });
+}
+
+// M x = b for a host symmetric positive definite M by the hand-written Cholesky, on buffers of its
+// own through the step's sequence (chol_factor_checked, chol_solve_checked): M and U column-major
+// n x n, upper triangles.  Needs a context only (no data).
+int scs_chol_eval(scs_ctx* c, int64_t n, const double* M, const double* b, double* x, double* U, int* info) {
+  return guarded(c, [&] {
+    if (n < 1 || !M || !b || !x) fail(c, SCS_ERR_ARG, "scs_chol_eval: bad arguments");
+    HCK(hipSetDevice(c->dev));
+    const int64_t np = round_up(n, 128);
+    if (c->ce_np != np) {
+      for (double** p : {&c->ceG, &c->ceW, &c->cey, &c->cerbk, &c->ceb}) dfree_t(c, *p);
+      dfree_t(c, c->cetri);
+      dfree_t(c, c->ceinfo);
+      chol_aux_free(&c->ceaux);
+      c->ce_np = 0;
+      const int nb = (int)(np / 128);
+      c->ceG = dalloc<double>(c, (size_t)np * np);
+      c->ceW = dalloc<double>(c, (size_t)np * 128);
+      c->cey = dalloc<double>(c, np);
+      c->cerbk = dalloc<double>(c, np);
+      c->ceb = dalloc<double>(c, np);
+      c->ceinfo = dalloc<int>(c, 1);
+      std::vector<int2> tr((size_t)nb * (nb + 1) / 2);
+      gram_tile_list_rowmajor(nb, tr.data());
+      c->cetri = dalloc<int2>(c, tr.size());
+      HCK(hipMemcpyAsync(c->cetri, tr.data(), sizeof(int2) * tr.size(), hipMemcpyHostToDevice, c->st));
+      HCK(chol_aux_init(&c->ceaux, np, c->st));   // (drains the stream: tr stays valid)
+      c->ce_np = np;
+    }
+    const CholSys s = {c->ceG, n, np, c->ceW, &c->ceaux, c->cetri, c->cey, c->cerbk, c->ceinfo};
+    double* bb = c->ceb;
+    auto upload = [&] {   // (also the system of a redo after a late chain wait, chol_factor_checked)
+      HCK(hipMemsetAsync(s.G, 0, sizeof(double) * np * np, c->st));
+      HCK(hipMemcpy2DAsync(s.G, sizeof(double) * np, M, sizeof(double) * n, sizeof(double) * n, n,
+                           hipMemcpyHostToDevice, c->st));
+      HCK(chol_diag_pad(s.G, np, n, np, c->st));
+    };
+    upload();
+    HCK(hipMemsetAsync(bb, 0, sizeof(double) * np, c->st));
+    HCK(hipMemcpyAsync(bb, b, sizeof(double) * n, hipMemcpyHostToDevice, c->st));
+    hipEvent_t e0;
+    tbegin(c, T_SOLVE, &e0);
+    const int hinfo = chol_factor_checked(c, s, upload);
+    if (hinfo == 0) chol_solve_checked(c, s, bb);
+    tend(c, T_SOLVE, e0);
+    if (hinfo == 0) HCK(hipMemcpyAsync(x, bb, sizeof(double) * n, hipMemcpyDeviceToHost, c->st));
+    if (U)
+      HCK(hipMemcpy2DAsync(U, sizeof(double) * n, s.G, sizeof(double) * np, sizeof(double) * n, n,
+                           hipMemcpyDeviceToHost, c->st));
+    sync(c);
+    if (info) *info = hinfo;
+    if (c->timing) tresolve(c);
+  });
+}
+
+// A x = b for a host row-major n x n A by the Householder QR, on buffers of its own through the
+// sample-space step's sequence (qr_from_rowmajor, qr_run); R column-major n x n, its upper triangle.
+// Needs a context only (no data).
+int scs_qr_eval(scs_ctx* c, int64_t n, const double* A, const double* b, double* x, double* R) {
+  return guarded(c, [&] {
+    if (n < 1 || !A || !b || !x) fail(c, SCS_ERR_ARG, "scs_qr_eval: bad arguments");
+    HCK(hipSetDevice(c->dev));
+    const int64_t np = round_up(n, 128);
+    if (c->qe_np != np) {
+      for (double** p : {&c->qeS, &c->qeA, &c->qeb}) dfree_t(c, *p);
+      c->qeS = dalloc<double>(c, (size_t)np * np);
+      c->qeA = dalloc<double>(c, (size_t)np * np);
+      c->qeb = dalloc<double>(c, np);
+      c->qe_np = np;
+    }
+    HCK(hipMemcpyAsync(c->qeS, A, sizeof(double) * n * n, hipMemcpyHostToDevice, c->st));
+    HCK(qr_from_rowmajor(c->qeS, n, c->qeA, np, n, np, c->st));
+    HCK(hipMemsetAsync(c->qeb, 0, sizeof(double) * np, c->st));
+    HCK(hipMemcpyAsync(c->qeb, b, sizeof(double) * n, hipMemcpyHostToDevice, c->st));
+    hipEvent_t e0;
+    tbegin(c, T_SOLVE, &e0);
+    qr_run(c, &c->qre, c->qebk, c->qebk_n, c->qeA, np, c->qeb);
+    tend(c, T_SOLVE, e0);
+    HCK(hipMemcpyAsync(x, c->qeb, sizeof(double) * n, hipMemcpyDeviceToHost, c->st));
+    if (R)
+      HCK(hipMemcpy2DAsync(R, sizeof(double) * n, c->qeA, sizeof(double) * np, sizeof(double) * n, n,
+                           hipMemcpyDeviceToHost, c->st));
+    sync(c);
     if (c->timing) tresolve(c);
   });
 }

@@ -181,6 +181,8 @@ _SIGS = {
     "scs_gemv_n_eval": (C.c_int, [C.c_void_p, c_dp, c_dp]),
     "scs_solve_eval": (C.c_int, [C.c_void_p, c_dp, c_dp, c_dp, C.c_int, c_dp, C.POINTER(C.c_int)]),
     "scs_lu_eval": (C.c_int, [C.c_void_p, C.c_int64, c_dp, c_dp, c_dp, c_i32p, C.POINTER(C.c_int)]),
+    "scs_chol_eval": (C.c_int, [C.c_void_p, C.c_int64, c_dp, c_dp, c_dp, c_dp, C.POINTER(C.c_int)]),
+    "scs_qr_eval": (C.c_int, [C.c_void_p, C.c_int64, c_dp, c_dp, c_dp, c_dp]),
     "scs_get_columns": (C.c_int, [C.c_void_p, c_i64p, C.c_int64, c_dp]),
     "scs_gram_atv_eval": (C.c_int, [C.c_void_p, c_dp, c_dp, c_i64p, C.c_int64, c_dp, c_dp, C.POINTER(C.c_int)]),
     "scs_multi_products_eval": (C.c_int, [C.c_void_p, C.c_int, c_dp, c_dp, c_dp, c_dp]),

@@ -962,3 +962,38 @@ def lu_solve(A, b, device=0, ctx=None):
                                    C.byref(info)))
     return (x if info.value == 0 else None), ipiv, int(info.value)
 
+
+def chol_solve(M, b, ctx=None, device=0):
+    """M x = b for a symmetric positive definite M (potrf + potrs, upper) on the device: the hand-written
+    blocked Cholesky (chol.hip) on the sequence a step runs, through the test door scs_chol_eval.  Only
+    M's upper triangle is read.  Returns (x, U, info): U the upper factor M = UᵀU (strict lower triangle
+    zeroed), info dpotrf's (the first non-positive pivot, 1-based; x is then None)."""
+    M = np.asarray(M, dtype=np.float64)
+    b = np.ascontiguousarray(b, dtype=np.float64).reshape(-1)
+    n = M.shape[0]
+    if M.shape != (n, n) or b.shape != (n,):
+        raise ValueError("M must be n x n and b of length n")
+    Mc = np.ascontiguousarray(M.T)   # the door's column-major M
+    ctx = ctx or _lib.Context(device)
+    x = np.zeros(n)
+    Uc = np.zeros((n, n))
+    info = C.c_int()
+    ctx.check(_lib.lib.scs_chol_eval(ctx.h, n, dptr(Mc), dptr(b), dptr(x), dptr(Uc), C.byref(info)))
+    return (x if info.value == 0 else None), np.triu(Uc.T), int(info.value)
+
+
+def qr_solve(A, b, ctx=None, device=0):
+    """A x = b for a dense square matrix by Householder QR (geqrf conventions) on the device (qr.hip),
+    on the sequence of the sample-space system, through the test door scs_qr_eval.  Returns (x, R): R
+    the upper triangular factor (strict lower triangle zeroed)."""
+    A = np.ascontiguousarray(A, dtype=np.float64)
+    b = np.ascontiguousarray(b, dtype=np.float64).reshape(-1)
+    n = A.shape[0]
+    if A.shape != (n, n) or b.shape != (n,):
+        raise ValueError("A must be n x n and b of length n")
+    ctx = ctx or _lib.Context(device)
+    x = np.zeros(n)
+    Rc = np.zeros((n, n))
+    ctx.check(_lib.lib.scs_qr_eval(ctx.h, n, dptr(A), dptr(b), dptr(x), dptr(Rc)))
+    return x, np.triu(Rc.T)
+
