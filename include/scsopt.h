@@ -260,7 +260,8 @@ int scs_set_loss_samplewise(scs_ctx* ctx, scs_samplewise_fn* fn, void* user, int
  * placed into the order-nvar system.  A stays on the device as one N x d block (fp64 or fp32
  * storage): the products A X and Aᵀ R read it once for all nout columns.
  * Refused with SCS_ERR_ARG: nout outside 2..16 (nout = 0 clears the mode); with nout set: a
- * sparse A (scs_set_sparse*, scs_gen_sparse), scs_gen_data, nranks > 1 and multi-device contexts,
+ * sparse A (scs_set_sparse*, scs_set_test_sparse*) unless scs_set_sparse_outputs is on (below),
+ * scs_gen_sparse, scs_gen_data, scs_set_compute_f32, nranks > 1 and multi-device contexts,
  * scs_set_batches, any other loss kind, and ProxGGNSCORE when N*nout + 1 <= d*nout (the reference
  * then takes its sample-space branch, whose step differs: use the callback loss for it).  The mode
  * persists across data doors, as scs_set_dense_f32 does.                                        */
@@ -271,6 +272,20 @@ int scs_set_loss_samplewise(scs_ctx* ctx, scs_samplewise_fn* fn, void* user, int
 int scs_set_outputs(scs_ctx* ctx, int nout);
 /* nout (1 when unset) and nvar = the length of x.  Either pointer may be NULL.                   */
 int scs_get_outputs(scs_ctx* ctx, int* nout, int64_t* nvar);
+/* Multi-output losses on a sparse A (opt-in; off by default).  With the mode on and nout set,
+ * scs_set_sparse / scs_set_sparse_device / scs_set_test_sparse / scs_set_test_sparse_device accept a
+ * sparse A of d columns (m = d at the door, y N x nout as above): the blocked copies are cut for
+ * nout right-hand sides and A X, Aᵀ R read the nonzeros once for all nout columns (per (row,
+ * column): entries in ascending index within each 16384-index group, groups summed in order; bitwise
+ * run to run).  The order-nvar system takes the sparse A's Gram routes on the d-column view.
+ * SCS_MULTI_SPARSE_KERNEL=0 (read at the data door) forms each column with the single-vector product
+ * instead.  ptr of the finer blocked copies grows to (sub-blocks x rows) int64 per direction.  Called
+ * before the data door; persists across doors; stored without effect while nout is unset; refused on
+ * multi-device contexts as scs_set_outputs is.  Still refused with nout set: scs_set_compute_f32,
+ * scs_gen_sparse / scs_gen_data, batches (scs_set_sparse_batches included), nranks > 1, the GGN
+ * sample-space shape and the single-vector kernel doors; scs_set_sparse_sample is stored without
+ * effect.                                                                                          */
+int scs_set_sparse_outputs(scs_ctx* ctx, int on);
 
 /* ---- data  (Problem(A, y, ...) -- problems.jl:61-81) --------------------- */
 /* Upload host A (column-major, N x m, leading dim lda) and y (N).  N is the
@@ -649,7 +664,9 @@ int scs_gram_atv_eval(scs_ctx* ctx, const double* w, const double* v, const int6
 
 /* Multi-output kernel-level doors (a dense A; K need not equal the context's nout).  X: d x K and
  * V: N x K, column-major; AX (N x K) = A X and ATV (d x K) = Aᵀ V, through the step's kernels.
- * 1 <= K <= 16.  Either pair (X, AX) / (V, ATV) may be NULL.                                      */
+ * 1 <= K <= 16.  Either pair (X, AX) / (V, ATV) may be NULL.  A sparse A held in the
+ * scs_set_sparse_outputs mode is served by the context's own product arm with K = nout; any other
+ * sparse context is refused with SCS_ERR_STATE.                                                    */
 int scs_multi_products_eval(scs_ctx* ctx, int K, const double* X, const double* V, double* AX, double* ATV);
 /* The assembled system of a multi-output context at x (nvar entries): G = JᵀQJ (nvar x nvar,
  * column-major, ldg >= nvar, both triangles) before λ diag Hr, g = vec(Aᵀ R) and *f = f(x).  Any

@@ -442,6 +442,22 @@ hipError_t launch_multi_weight(int loss, const double* P, const double* s, int k
 hipError_t launch_multi_place(const double* Gd, int64_t ldd, int64_t d, int k, int l, double* G, int64_t ldg,
                               hipStream_t st);
 
+// ---- multi_sparse.hip: the same two products on a sparse A (scs_set_sparse_outputs), one pass over the
+// nonzeros for all K columns.  The blocked copy is build_blocked's at shift multi_spmm_shift(ncols, K)
+// (sub-blocks of 2^shift indices, KP = multi_spmm_group(K) of them per group); Xt is the packed operand
+// (ncols x KP, zero beyond column K: launch_multi_spmm_pack from a column-major source with column stride
+// ld, rows nvalid..ntotal zero); out[(g*K + l)*ldo + r] = Σ_{p in row r, group g} val[p] Xt[index(p)*KP + l]
+int multi_spmm_shift(int64_t ncols, int K);
+int multi_spmm_group(int K);
+// the default arm for K columns of f32 / fp64 values: 1 the one-pass kernel, 0 K single-vector launches
+int multi_spmm_default(int K, int f32);
+hipError_t launch_multi_spmm_pack(const double* src, int64_t ld, int64_t nvalid, int64_t ntotal, int K, double* dst,
+                                  hipStream_t st);
+const char* multi_spmm_kernel_name(int f32, int K);
+hipError_t launch_multi_spmm(const int64_t* ptr, const uint16_t* lidx, const void* val, int f32, const double* Xt,
+                             int K, int64_t nrows, int64_t ncols, int shift, double* out, int64_t ldo,
+                             hipStream_t st);
+
 // ---- sparse.hip (LDS-blocked gathers; out[b*ldo + r] = Σ_{p in row r, block b} val[p] x[(b<<shift) + lidx[p]])
 int spmv_blk_shift(int64_t ncols);
 int spmv_pad_index();   // padding index of the blocked layouts (the SpMV's zero slot)

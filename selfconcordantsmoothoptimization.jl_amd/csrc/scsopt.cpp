@@ -66,6 +66,10 @@ struct DevBuf {
 // an LDS-blocked copy of a sparse A (sparse.hip)
 struct SpBlkT {
   int shift = 0, nblk = 0;
+  // blocks per partial: 1 in the single-vector layout; the K-column layout of a multi-output context
+  // (scs_set_sparse_outputs, multi_sparse.hip) cuts each 16384-index block into kp sub-blocks and the
+  // products still write one partial per group of kp
+  int kp = 1;
   int64_t nnz = 0;   // entries of the copy
   int64_t* ptr = nullptr;
   uint16_t* lidx = nullptr;
@@ -136,6 +140,12 @@ struct scs_ctx {
   // everything after the products.
   int nout = 0;
   int64_t dc = 0, dcp = 0;
+  // scs_set_sparse_outputs: with nout set the sparse doors are accepted and the products of a sparse A
+  // run with K right-hand sides (stored without effect while nout is unset).  ms_kernel: the arm read
+  // at the data door (SCS_MULTI_SPARSE_KERNEL / multi_spmm_default): 1 the one-pass kernel on the
+  // K-column blocked copies, 0 K launches of the single-vector product on the single-vector copies
+  int sparse_outputs = 0;
+  int ms_kernel = 0;
   double* mXt = nullptr;   // x = vec(X) repacked K-contiguous (dcp x K, zero beyond dc): launch_multi_pack_x
   double* mVt = nullptr;   // an N x K operand of Aᵀ V repacked K-contiguous (grow-only, mVt_cap doubles)
   int64_t mVt_cap = 0;
@@ -673,6 +683,8 @@ bool sharded(const scs_ctx* c) { return c->nranks > 1 || c->comm_force; }
 int kout(const scs_ctx* c) { return c->nout ? c->nout : 1; }
 bool multi(const scs_ctx* c) { return c->nout >= 2; }
 bool multi_loss(int loss) { return loss == SCS_LOSS_SOFTMAX_CE || loss == SCS_LOSS_MULTI_LS; }
+// the partials a product on the blocked copy B writes per row (one per group of B.kp blocks)
+int blk_groups(const SpBlkT& B) { return (B.nblk + B.kp - 1) / B.kp; }
 
 // doubles of the in-place all-reduce payload: packed Gram tiles ‖ Aᵀv (GGN / NSCORE), the
 // m-vector (LQN), or the all-gather of the rows for the sharded GGN sample-space branch
@@ -758,7 +770,9 @@ void alloc_mspace(scs_ctx* c) {
   dfree_t(c, c->lqR);
   c->lqR = dalloc<double>(c, (size_t)LQ_NPART * LQ_G);
   dfree_t(c, c->mXt);
-  if (multi(c)) c->mXt = dalloc<double>(c, (size_t)c->dcp * c->nout);
+  // (16 columns whatever nout: a sparse A's -- or a sparse held-out set's, whose mode may be switched on
+  // after this door -- one-pass kernel takes the pack padded to KP <= 16 columns, multi_sparse.hip)
+  if (multi(c)) c->mXt = dalloc<double>(c, (size_t)c->dcp * 16);
   if (!c->hscal) HCK(hipHostMalloc((void**)&c->hscal, 64 * sizeof(double), hipHostMallocDefault));
   if (!c->hserr) {
     HCK(hipHostMalloc((void**)&c->hserr, sizeof(int), hipHostMallocDefault));
@@ -774,9 +788,9 @@ void alloc_nspace(scs_ctx* c) {
   if (c->generic) return;
   ++c->y_stamp;   // a new view: its y is (re)written by the caller of this function
   const int64_t K = kout(c);   // multi-output: Z, R, P are N x K (stride Npad), the partials K columns per slice
-  c->nsplit = c->sparse ? c->bcsr.nblk : gemv_n_splits(c->Npad, c->dc);
+  c->nsplit = c->sparse ? blk_groups(c->bcsr) : gemv_n_splits(c->Npad, c->dc);
   c->nval = epilogue_blocks(c->Npad);
-  c->nchunk = c->sparse ? c->bcsc.nblk : multi(c) ? multi_atv_chunks(c->Npad) : gemv_t_chunks(c->Npad);
+  c->nchunk = c->sparse ? blk_groups(c->bcsc) : multi(c) ? multi_atv_chunks(c->Npad) : gemv_t_chunks(c->Npad);
   dfree_t(c, c->zpart);
   dfree_t(c, c->z);
   dfree_t(c, c->gN);
@@ -1510,6 +1524,22 @@ const char* const GEMV_N_F32_NAME = "gemv_n_kernel<float>";
 // z-partials of A x into c->zpart (dense: `nsplit` column splits; sparse: one
 // CSR gather pass).  Returns the number of partials written.
 int matvec_n(scs_ctx* c, const double* xd, int nsplit) {
+  if (c->sparse && multi(c)) {   // Z = A X on the blocked CSR: part[(group*K + l)*Npad + n]
+    const auto& B = c->bcsr;
+    const int K = c->nout;
+    if (B.kp > 1) {   // one pass over the nonzeros for all K columns (multi_sparse.hip)
+      HCK(launch_multi_spmm_pack(xd, c->dc, c->dc, c->dcp, K, c->mXt, c->st));
+      HCK(launch_multi_spmm(B.ptr, B.lidx, B.val, c->sp_f32, c->mXt, K, c->N, c->dc, B.shift, c->zpart, c->Npad,
+                            c->st));
+      c->prod_kname = multi_spmm_kernel_name(c->sp_f32, K);
+    } else {          // the loop arm: column l of vec(X) is contiguous at x + d*l
+      for (int l = 0; l < K; ++l)
+        HCK(launch_spmv_blk(B.ptr, B.lidx, B.val, c->sp_f32, xd + c->dc * l, c->N, c->dc, B.shift, c->nnz,
+                            c->zpart + (int64_t)l * c->Npad, (int64_t)K * c->Npad, c->st));
+      c->prod_kname = spmv_kernel_name(c->sp_f32);
+    }
+    return blk_groups(B);
+  }
   if (c->sparse) {
     const auto& B = c->bcsr;
     const int vk = c->sp_f32 ? (c->f32c ? 2 : 1) : 0;
@@ -1529,6 +1559,8 @@ int matvec_n(scs_ctx* c, const double* xd, int nsplit) {
 
 // the partial rows of Aᵀ v over the local rows into c->tpart (stride mpad); returns their count
 int matvec_t_part(scs_ctx* c, const double* v) {
+  if (c->sparse && multi(c))
+    fail(c, SCS_ERR_ARG, "internal: the single-vector Aᵀv partials do not serve a multi-output context");
   if (c->sparse) {
     const auto& B = c->bcsc;
     const int vk = c->sp_f32 ? (c->f32c ? 2 : 1) : 0;
@@ -1554,6 +1586,21 @@ double* multi_vt(scs_ctx* c, int64_t need) {
 // out (device, m) = Aᵀ v over the local rows (dense: chunked column sums +
 // fixed-order finalize; sparse: one CSC gather pass)
 void matvec_t(scs_ctx* c, const double* v, double* out) {
+  if (multi(c) && c->sparse) {   // vec(Aᵀ V) on the blocked CSC: part[(group*K + l)*dcp + j]
+    const auto& B = c->bcsc;
+    const int K = c->nout;
+    if (B.kp > 1) {
+      double* Vt = multi_vt(c, c->Npad * B.kp);
+      HCK(launch_multi_spmm_pack(v, c->Npad, c->Npad, c->Npad, K, Vt, c->st));
+      HCK(launch_multi_spmm(B.ptr, B.lidx, B.val, c->sp_f32, Vt, K, c->dc, c->N, B.shift, c->tpart, c->dcp, c->st));
+    } else {
+      for (int l = 0; l < K; ++l)
+        HCK(launch_spmv_blk(B.ptr, B.lidx, B.val, c->sp_f32, v + (int64_t)l * c->Npad, c->dc, c->N, B.shift, c->nnz,
+                            c->tpart + (int64_t)l * c->dcp, (int64_t)K * c->dcp, c->st));
+    }
+    HCK(launch_multi_atv_finalize(c->tpart, blk_groups(B), K, c->dcp, c->dc, out, c->st));
+    return;
+  }
   if (multi(c)) {   // vec(Aᵀ V), V N x K (stride Npad): chunk partials of all K columns in one pass over A
     const int K = c->nout;
     double* Vt = multi_vt(c, c->Npad * K);
@@ -2257,7 +2304,7 @@ int dense_a32(const scs_ctx* c) { return c->sparse ? 0 : c->a32; }
 const double* dense_A(scs_ctx* c) {
   if (!c->sparse) return c->A;
   if (c->Ad) return c->Ad;
-  const size_t bytes = (size_t)c->Npad * c->mpad * sizeof(double);
+  const size_t bytes = (size_t)c->Npad * c->dcp * sizeof(double);   // the data view's columns
   size_t fr = 0, tot = 0;
   HCK(hipMemGetInfo(&fr, &tot));
   if (bytes + (size_t)c->mpad * c->mpad * 16 > fr)
@@ -2280,7 +2327,7 @@ void build_gram_blocked(scs_ctx* c) {
   scs_ctx::SpBlk& B = c->bgram;
   const int64_t nrows = c->N;
   B.shift = sparse_gram_shift();
-  B.nblk = (int)ceil_div(c->m, int64_t(1) << B.shift);
+  B.nblk = (int)ceil_div(c->dc, int64_t(1) << B.shift);
   const int64_t nk = (int64_t)B.nblk * nrows;
   int64_t* cnt = dalloc<int64_t>(c, nk + 1);
   int64_t* first = dalloc<int64_t>(c, nk + 1);
@@ -2313,7 +2360,7 @@ bool build_gram_seg(scs_ctx* c) {
   scs_ctx::SegGram& S = c->sgseg;
   if (S.state) return S.state > 0;
   S.state = -1;
-  const int64_t nrows = c->N, m = c->m;
+  const int64_t nrows = c->N, m = c->dc;   // the data view's columns
   const int shift = sparse_gram_shift();
   const int64_t nblk = ceil_div(m, int64_t(1) << shift);
   const int64_t nk = nblk * nrows;
@@ -2369,7 +2416,7 @@ bool sparse_gram(scs_ctx* c) {
     sync(c);
     double s2 = 0.0;
     for (int64_t r = 0; r < c->N; ++r) s2 += (double)(rp[r + 1] - rp[r]) * (double)(rp[r + 1] - rp[r]);
-    c->sp_gram = (64.0 * s2 <= (double)c->N * (double)c->m * (double)c->m) ? 1 : 2;
+    c->sp_gram = (64.0 * s2 <= (double)c->N * (double)c->dc * (double)c->dc) ? 1 : 2;
   }
   return c->sp_gram == 1;
 }
@@ -2381,16 +2428,16 @@ void gram_sparse(scs_ctx* c, const double* w, double* out, int packed) {
   if (sparse_gram_requested() == 8 && build_gram_seg(c)) {   // variant 8 (default)
     const scs_ctx::SegGram& S = c->sgseg;
     HCK(csc_weight(c->rowidx, c->valT, c->sp_f32, w, c->nnz, S.sw, c->st));
-    HCK(launch_sparse_gram_seg(c->colptr, S.sw, S.tptr, S.T, S.seg, c->sp_f32, c->m, S.shift, dst, c->mpad, c->st));
+    HCK(launch_sparse_gram_seg(c->colptr, S.sw, S.tptr, S.T, S.seg, c->sp_f32, c->dc, S.shift, dst, c->dcp, c->st));
     c->gram_kname = c->sp_f32 ? "sparse_gram_seg_kernel<float, 0>" : "sparse_gram_seg_kernel<double, 0>";   // rocprofv3's names
-    if (packed & 1) HCK(gram_pack_launch(c->G, c->mpad, c->utiles, c->nslots, out, c->st));
+    if (packed & 1) HCK(gram_pack_launch(c->G, c->dcp, c->utiles, c->nslots, out, c->st));
     return;
   }
   if (!c->bgram.ptr) build_gram_blocked(c);
   HCK(launch_sparse_gram(c->colptr, c->rowidx, c->valT, c->bgram.ptr, c->bgram.lidx, c->bgram.val, c->bgram.nnz,
-                         c->sp_f32, w, c->N, c->m, c->bgram.shift, dst, c->mpad, c->st));
+                         c->sp_f32, w, c->N, c->dc, c->bgram.shift, dst, c->dcp, c->st));
   c->gram_kname = sparse_gram_kernel_name(c->sp_f32, c->bgram.nnz);
-  if (packed & 1) HCK(gram_pack_launch(c->G, c->mpad, c->utiles, c->nslots, out, c->st));
+  if (packed & 1) HCK(gram_pack_launch(c->G, c->dcp, c->utiles, c->nslots, out, c->st));
 }
 
 // How the Gram of a sparse A gets its dense operand tiles: a mirror of all of A when it fits
@@ -2399,7 +2446,7 @@ void gram_sparse(scs_ctx* c, const double* w, double* out, int packed) {
 bool sparse_streams(scs_ctx* c) {
   if (!c->sparse) return false;
   if (c->sp_mode == 0) {
-    const double bytes = (double)c->Npad * c->mpad * sizeof(double);
+    const double bytes = (double)c->Npad * c->dcp * sizeof(double);   // the mirror of the data view
     size_t fr = 0, tot = 0;
     HCK(hipMemGetInfo(&fr, &tot));
     double cap = (double)fr - (double)c->mpad * c->mpad * 24 - 4.0 * 1073741824.0;
@@ -2422,17 +2469,17 @@ void gram_main_stream(scs_ctx* c, const double* w, double* out, int packed) {
       size_t fr = 0, tot = 0;
       HCK(hipMemGetInfo(&fr, &tot));
       const double budget = std::min(16.0 * 1073741824.0, 0.25 * (double)fr);
-      R = std::max<int64_t>(2048, (int64_t)(budget / (2.0 * c->mpad * sizeof(double))) / 2048 * 2048);
+      R = std::max<int64_t>(2048, (int64_t)(budget / (2.0 * c->dcp * sizeof(double))) / 2048 * 2048);
     }
     c->ring_rows = std::min(R, c->Npad);
-    c->ringA = dalloc<double>(c, (size_t)2 * c->ring_rows * c->mpad);
+    c->ringA = dalloc<double>(c, (size_t)2 * c->ring_rows * c->dcp);
     c->ring_r0[0] = c->ring_r0[1] = -1;
   }
   const int64_t R = c->ring_rows;
   const int64_t nchunk = ceil_div(std::max<int64_t>(c->N, 1), R);
   for (int64_t k = 0; k < nchunk; ++k) {
     const int s = (int)(k & 1);
-    double* slot = c->ringA + (size_t)s * R * c->mpad;
+    double* slot = c->ringA + (size_t)s * R * c->dcp;
     const int64_t r0 = k * R, n = std::min(R, c->N - r0);
     if (c->ring_r0[s] >= 0)
       HCK(launch_densify_range(c->rowptr, c->colidx, c->val, c->sp_f32, c->ring_r0[s], c->ring_n[s], R, 1, slot, c->st));
@@ -2445,10 +2492,10 @@ void gram_main_stream(scs_ctx* c, const double* w, double* out, int packed) {
     if (c->gwork)
       HCK(gram_launch_sched(slot, 0, R / 16, w + r0, nk, pr ? c->pwork : c->gwork, pr ? c->pseglen : c->gseglen,
                             pr ? c->pnsplit : c->gnsplit, pr ? c->pcomb : c->gcomb, pr ? c->pncomb : c->gncomb,
-                            c->gpart, out, c->mpad, mode, c->tall, c->st));
+                            c->gpart, out, c->dcp, mode, c->tall, c->st));
     else
       HCK(gram_launch(slot, 0, R / 16, w + r0, nk, pr ? c->ptiles : c->tiles, pr ? c->nptiles : c->ntiles, out,
-                      c->mpad, mode, c->tall, c->st));
+                      c->dcp, mode, c->tall, c->st));
     c->gram_kname = gram_main_kernel_name();
   }
 }
@@ -3415,6 +3462,29 @@ static void refuse_multi(scs_ctx* c, const char* what) {
   if (multi(c)) fail(c, SCS_ERR_ARG, "%s is not supported with scs_set_outputs (nout = %d)", what, c->nout);
 }
 
+// a sparse door on a multi-output context: accepted in the scs_set_sparse_outputs mode (one rank)
+static void refuse_multi_sparse(scs_ctx* c, const char* what, int64_t N, int64_t Nglob, int64_t row0) {
+  if (!multi(c)) return;
+  if (!c->sparse_outputs)
+    fail(c, SCS_ERR_ARG, "%s is not supported with scs_set_outputs (nout = %d); pass sparse_outputs=True / "
+                         "scs_set_sparse_outputs", what, c->nout);
+  if (c->nranks > 1 || (Nglob > 0 && Nglob != N) || row0 != 0)
+    fail(c, SCS_ERR_ARG, "scs_set_outputs (nout = %d) runs on one rank: nranks > 1 / a row shard is not supported",
+         c->nout);
+  if (c->f32c)
+    fail(c, SCS_ERR_ARG, "scs_set_compute_f32 (the fp32-arithmetic products have one right-hand side) is not "
+                         "supported with scs_set_outputs (nout = %d)", c->nout);
+}
+
+// Which arm forms the products of a sparse A with K right-hand sides: 1 the one-pass kernel
+// (multi_sparse.hip), 0 K launches of the single-vector product.  SCS_MULTI_SPARSE_KERNEL=0 / 1 forces
+// an arm (read at the data door); the default is the measured one per K and storage type
+// (multi_spmm_default in multi_sparse.hip, the one place of the rule; DESIGN §2i, products table).
+static int multi_sparse_arm(int K, int f32) {
+  if (const char* e = std::getenv("SCS_MULTI_SPARSE_KERNEL")) return e[0] != '0';
+  return multi_spmm_default(K, f32);
+}
+
 static void set_dims(scs_ctx* c, int64_t N, int64_t m, int64_t Nglob, int64_t row0) {
   if (m <= 0 || N < 0) fail(c, SCS_ERR_ARG, "bad dimensions N=%lld m=%lld", (long long)N, (long long)m);
   c->N = N;
@@ -3907,8 +3977,9 @@ static void upload_vals(scs_ctx* c, void* dst, const double* src, int64_t n, int
 
 // Sort each row's entries by index (in place: the arrays are replaced by sorted
 // copies) and build the LDS-blocked copy B (sparse.hip).
+// kcols > 1: the K-column layout of multi_sparse.hip (finer blocks, the same slots and padding).
 static void build_blocked(scs_ctx* c, int64_t nrows, int64_t ncols, int64_t* ptr, int*& idx, void*& val,
-                          scs_ctx::SpBlk& B) {
+                          scs_ctx::SpBlk& B, int kcols = 1) {
   const int64_t nnz = c->nnz;
   size_t tb = 0;
   if (nnz > 0 && nrows > 0) {
@@ -3926,7 +3997,8 @@ static void build_blocked(scs_ctx* c, int64_t nrows, int64_t ncols, int64_t* ptr
     idx = idx_s;
     val = val_s;
   }
-  B.shift = spmv_blk_shift(ncols);
+  B.shift = kcols > 1 ? multi_spmm_shift(ncols, kcols) : spmv_blk_shift(ncols);
+  B.kp = kcols > 1 ? multi_spmm_group(kcols) : 1;
   B.nblk = (int)ceil_div(ncols, int64_t(1) << B.shift);
   const int64_t nk = (int64_t)B.nblk * nrows;
   int64_t* cnt = dalloc<int64_t>(c, nk + 1);
@@ -3963,7 +4035,7 @@ static void build_blocked(scs_ctx* c, int64_t nrows, int64_t ncols, int64_t* ptr
 // (scs_set_sparse_device): claim, scan, place (sparse.hip).  Columns come out in arrival order of
 // their runs; the stable sort of build_blocked on the CSC copy makes the order the host door's.
 static void transpose_csr(scs_ctx* c) {
-  const int64_t N = c->N, m = c->m, nnz = c->nnz;
+  const int64_t N = c->N, m = c->dc, nnz = c->nnz;   // the data view's columns
   c->colptr = dalloc<int64_t>(c, m + 1);
   c->rowidx = dalloc<int>(c, nnz, false);
   c->valT = c->sp_f32 ? (void*)dalloc<float>(c, (size_t)nnz, false) : (void*)dalloc<double>(c, (size_t)nnz, false);
@@ -3985,18 +4057,21 @@ static void transpose_csr(scs_ctx* c) {
 // what scs_set_sparse and scs_set_sparse_device share once rowptr / colidx / val (and, from the host,
 // colptr / rowidx / valT) and y are in place
 static void finish_sparse(scs_ctx* c, bool transpose) {
-  build_blocked(c, c->N, c->m, c->rowptr, c->colidx, c->val, c->bcsr);
+  c->ms_kernel = multi(c) ? multi_sparse_arm(c->nout, c->sp_f32) : 0;   // read once, here: one set of copies per context
+  const int kc = c->ms_kernel ? c->nout : 1;
+  build_blocked(c, c->N, c->dc, c->rowptr, c->colidx, c->val, c->bcsr, kc);
   if (transpose) transpose_csr(c);
-  build_blocked(c, c->m, c->N, c->colptr, c->rowidx, c->valT, c->bcsc);
+  build_blocked(c, c->dc, c->N, c->colptr, c->rowidx, c->valT, c->bcsc, kc);
   alloc_mspace(c);
   alloc_nspace(c);
   sync(c);
   c->has_data = true;
 }
 
-// the held-out counterpart: CSR only
-static void finish_sparse_test(scs_ctx* c, int64_t N) {
-  build_blocked(c, N, c->m, c->rowptr, c->colidx, c->val, c->bcsr);
+// the held-out counterpart: CSR only (the arm of a sparse A's context is the one its data door read)
+static void finish_sparse_test(scs_ctx* c, int64_t N, bool data_sparse) {
+  const int arm = !multi(c) ? 0 : data_sparse ? c->ms_kernel : multi_sparse_arm(c->nout, c->sp_f32);
+  build_blocked(c, N, c->dc, c->rowptr, c->colidx, c->val, c->bcsr, arm ? c->nout : 1);
   alloc_nspace(c);
   sync(c);
   c->tset.on = true;
@@ -4006,7 +4081,7 @@ int scs_set_sparse(scs_ctx* c, int64_t N, int64_t m, int64_t nnz, const int64_t*
                    const double* val, const int64_t* colptr, const int32_t* rowidx, const double* valT, int f32,
                    const double* y, int64_t Nglob, int64_t row0) {
   return guarded(c, [&] {
-    refuse_multi(c, "a sparse A (scs_set_sparse)");
+    refuse_multi_sparse(c, "a sparse A (scs_set_sparse)", N, Nglob, row0);
     if (nnz < 0 || !rowptr || !colptr || (nnz > 0 && (!colidx || !val || !rowidx || !valT)))
       fail(c, SCS_ERR_ARG, "sparse A: null arrays");
     if (rowptr[0] != 0 || rowptr[N] != nnz || colptr[0] != 0 || colptr[m] != nnz)
@@ -4040,8 +4115,13 @@ int scs_set_sparse(scs_ctx* c, int64_t N, int64_t m, int64_t nnz, const int64_t*
       upload_vals(c, c->val, val, nnz, c->sp_f32);
       upload_vals(c, c->valT, valT, nnz, c->sp_f32);
     }
-    c->y = dalloc<double>(c, c->Npad);
-    if (y && N > 0) h2d(c, c->y, y, N);
+    c->y = dalloc<double>(c, c->Npad * kout(c));
+    if (y && N > 0 && multi(c)) {   // N x nout, column-major
+      copy_y_any(c, y, N);
+      sync(c);   // a pageable host source: the call returns with the copy done
+    } else if (y && N > 0) {
+      h2d(c, c->y, y, N);
+    }
     finish_sparse(c, false);
   });
 }
@@ -4151,7 +4231,7 @@ int scs_set_sparse_device(scs_ctx* c, int64_t N, int64_t m, int64_t nnz, const v
                     "scs_set_sparse_device"};
   if (is_group(c)) return refuse_group_device(c, s.what);
   return guarded(c, [&] {
-    refuse_multi(c, "a sparse A (scs_set_sparse_device)");
+    refuse_multi_sparse(c, "a sparse A (scs_set_sparse_device)", N, Nglob, row0);
     HCK(hipSetDevice(c->dev));
     check_sparse_src(c, s, N, m, nnz);
     const CsrBufs b = ingest_csr(c, s, N, m, nnz, f32 ? 1 : 0);
@@ -4164,7 +4244,7 @@ int scs_set_sparse_device(scs_ctx* c, int64_t N, int64_t m, int64_t nnz, const v
     c->rowptr = b.rowptr;
     c->colidx = b.colidx;
     c->val = b.val;
-    c->y = dalloc<double>(c, c->Npad);
+    c->y = dalloc<double>(c, c->Npad * kout(c));
     copy_y_any(c, y, N);
     finish_sparse(c, true);
   });
@@ -4249,7 +4329,7 @@ int scs_get_sparse(scs_ctx* c, int64_t* rowptr, int32_t* colidx, double* val) {
 }
 
 int scs_get_sparse_csc(scs_ctx* c, int64_t* colptr, int32_t* rowidx, double* valT) {
-  return guarded(c, [&] { get_compressed(c, c->m, c->colptr, c->rowidx, c->valT, colptr, rowidx, valT); });
+  return guarded(c, [&] { get_compressed(c, c->dc, c->colptr, c->rowidx, c->valT, colptr, rowidx, valT); });
 }
 
 // ---- held-out data (Problem(...; Atest, ytest), problems.jl:27-28,67-68) -----------------------
@@ -4331,7 +4411,7 @@ int scs_set_test_sparse(scs_ctx* c, int64_t N, int64_t nnz, const int64_t* rowpt
     return SCS_ERR_ARG;
   }
   return guarded(c, [&] {
-    refuse_multi(c, "sparse held-out rows (scs_set_test_sparse)");
+    refuse_multi_sparse(c, "sparse held-out rows (scs_set_test_sparse)", N, Nglob, 0);
     HCK(hipSetDevice(c->dev));
     free_test(c);
     if (!rowptr || !y || nnz < 0 || (nnz > 0 && (!colidx || !val)))
@@ -4341,11 +4421,12 @@ int scs_set_test_sparse(scs_ctx* c, int64_t N, int64_t nnz, const int64_t* rowpt
     for (int64_t i = 0; i < N; ++i)
       if (rowptr[i + 1] < rowptr[i]) fail(c, SCS_ERR_ARG, "sparse test data: rowptr not monotone at %lld", (long long)i);
     for (int64_t p = 0; p < nnz; ++p)
-      if (colidx[p] < 0 || colidx[p] >= c->m)
+      if (colidx[p] < 0 || colidx[p] >= c->dc)
         fail(c, SCS_ERR_ARG, "sparse test data: column index out of range at %lld", (long long)p);
     if (nnz > INT32_MAX * 64LL) fail(c, SCS_ERR_ARG, "sparse test data: nnz too large");
     (void)row0;
     test_view_dims(c, N, Nglob, true);
+    const bool data_sparse = c->sparse;
     TestScope ts(c);
     c->sp_f32 = f32 ? 1 : 0;
     c->nnz = nnz;
@@ -4357,8 +4438,13 @@ int scs_set_test_sparse(scs_ctx* c, int64_t N, int64_t nnz, const int64_t* rowpt
       HCK(hipMemcpyAsync(c->colidx, colidx, sizeof(int) * nnz, hipMemcpyHostToDevice, c->st));
       upload_vals(c, c->val, val, nnz, c->sp_f32);
     }
-    if (N > 0) h2d(c, c->y, y, N);
-    finish_sparse_test(c, N);
+    if (N > 0 && multi(c)) {   // N x nout, column-major
+      copy_y_any(c, y, N);
+      sync(c);
+    } else if (N > 0) {
+      h2d(c, c->y, y, N);
+    }
+    finish_sparse_test(c, N, data_sparse);
   });
 }
 
@@ -4370,16 +4456,17 @@ int scs_set_test_sparse_device(scs_ctx* c, int64_t N, int64_t nnz, const void* d
                     "scs_set_test_sparse_device"};
   if (is_group(c)) return refuse_group_device(c, s.what);
   return guarded(c, [&] {
-    refuse_multi(c, "sparse held-out rows (scs_set_test_sparse_device)");
+    refuse_multi_sparse(c, "sparse held-out rows (scs_set_test_sparse_device)", N, Nglob, 0);
     HCK(hipSetDevice(c->dev));
     if (!y) fail(c, SCS_ERR_ARG, "%s: y is NULL (the CSR arrays and y are both required)", s.what);
     if (!c->has_data || c->generic)
       fail(c, SCS_ERR_STATE, "test data needs a data problem: call scs_set_data / scs_gen_data / scs_set_sparse first");
-    check_sparse_src(c, s, N, c->m, nnz);
-    const CsrBufs b = ingest_csr(c, s, N, c->m, nnz, f32 ? 1 : 0);
+    check_sparse_src(c, s, N, c->dc, nnz);
+    const CsrBufs b = ingest_csr(c, s, N, c->dc, nnz, f32 ? 1 : 0);
     free_test(c);
     (void)row0;
     test_view_dims(c, N, Nglob, true);
+    const bool data_sparse = c->sparse;
     TestScope ts(c);
     c->sp_f32 = f32 ? 1 : 0;
     c->nnz = nnz;
@@ -4387,7 +4474,7 @@ int scs_set_test_sparse_device(scs_ctx* c, int64_t N, int64_t nnz, const void* d
     c->colidx = b.colidx;
     c->val = b.val;
     copy_y_any(c, y, N);
-    finish_sparse_test(c, N);
+    finish_sparse_test(c, N, data_sparse);
   });
 }
 
@@ -4611,6 +4698,7 @@ int scs_set_reg(scs_ctx* c, int reg, const double* lam, int nlam, const double* 
 int scs_set_compute_f32(scs_ctx* c, int on) {
   if (is_group(c)) return group_run(c, [&](scs_ctx* s_, int) { return scs_set_compute_f32(s_, on); });
   return guarded(c, [&] {
+    if (on) refuse_multi(c, "scs_set_compute_f32 (the fp32-arithmetic products have one right-hand side)");
     sync(c);
     c->f32c = on ? 1 : 0;
     invalidate_caches(c);
@@ -5788,15 +5876,58 @@ int scs_get_outputs(scs_ctx* c, int* nout, int64_t* nvar) {
   });
 }
 
-// A X (N x K) and Aᵀ V (d x K) of host operands through multi.hip's kernels; K is the call's own
+// The mode of a sparse A under scs_set_outputs: stored without effect while nout is unset; with nout
+// set the sparse doors accept A and the products run with K right-hand sides (multi_sparse.hip).
+int scs_set_sparse_outputs(scs_ctx* c, int on) {
+  if (!c) return SCS_ERR_ARG;
+  if (is_group(c)) {
+    c->err = "scs_set_sparse_outputs takes a single-device context (scs_create): a multi-device context "
+             "(devices=[...]) is not supported with nout";
+    return SCS_ERR_ARG;
+  }
+  return guarded(c, [&] { c->sparse_outputs = on ? 1 : 0; });
+}
+
+// A X (N x K) and Aᵀ V (d x K) of host operands through multi.hip's kernels; K is the call's own.  A
+// sparse A held in the scs_set_sparse_outputs mode: through the context's own product arm, K = nout.
 int scs_multi_products_eval(scs_ctx* c, int K, const double* X, const double* V, double* AX, double* ATV) {
   return guarded(c, [&] {
-    if (!c->has_data || c->generic || c->sparse) fail(c, SCS_ERR_STATE, "scs_multi_products_eval needs a dense A");
+    if (!c->has_data || c->generic || (c->sparse && !multi(c)))
+      fail(c, SCS_ERR_STATE, "scs_multi_products_eval needs a dense A");
     if (K < 1 || K > 16) fail(c, SCS_ERR_ARG, "scs_multi_products_eval: K = %d is outside 1..16", K);
     if ((X == nullptr) != (AX == nullptr) || (V == nullptr) != (ATV == nullptr))
       fail(c, SCS_ERR_ARG, "scs_multi_products_eval: X goes with AX and V with ATV");
     HCK(hipSetDevice(c->dev));
     const int64_t N = c->N, Npad = c->Npad, d = c->dc, dcp = c->dcp;
+    if (c->sparse) {   // the step's own matvec_n / matvec_t on the context's workspace
+      if (K != c->nout)
+        fail(c, SCS_ERR_ARG, "scs_multi_products_eval: a sparse A takes K = nout = %d (the blocked copies are cut "
+                             "for it), not K = %d", c->nout, K);
+      invalidate_caches(c);
+      if (X) {
+        double* Z = dalloc<double>(c, (size_t)K * Npad);
+        h2d(c, c->xn, X, d * K);
+        const int ns = matvec_n(c, c->xn, c->nsplit);
+        HCK(launch_multi_epilogue(SCS_LOSS_MULTI_LS, EPI_Z, K, c->zpart, ns, nullptr, N, Npad, 1.0, Z, nullptr, nullptr,
+                                  nullptr, nullptr, c->st));
+        if (N > 0)
+          HCK(hipMemcpy2DAsync(AX, sizeof(double) * N, Z, sizeof(double) * Npad, sizeof(double) * N, K,
+                               hipMemcpyDeviceToHost, c->st));
+        sync(c);
+        dfree_t(c, Z);
+      }
+      if (V) {
+        double* dV = dalloc<double>(c, (size_t)Npad * K);   // zeroed: rows N..Npad stay zero
+        if (N > 0)
+          HCK(hipMemcpy2DAsync(dV, sizeof(double) * Npad, V, sizeof(double) * N, sizeof(double) * N, K,
+                               hipMemcpyHostToDevice, c->st));
+        matvec_t(c, dV, c->gtmp2);
+        d2h(c, ATV, c->gtmp2, d * K);
+        sync(c);
+        dfree_t(c, dV);
+      }
+      return;
+    }
     if (X) {
       const int ns = gemv_n_splits(Npad, d);
       double* dX = dalloc<double>(c, (size_t)d * K);

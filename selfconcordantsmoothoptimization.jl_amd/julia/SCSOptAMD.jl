@@ -436,6 +436,57 @@ function DeviceProblem(rowptr::Ptr{Cvoid}, colidx::Ptr{Cvoid}, val::Ptr{Cvoid}, 
     return finish_problem(ctx, nothing, y isa Ptr ? nothing : yroot, x0, loss, λ, out_fn, scale, L, sol, C_set, P)
 end
 
+# A multi-output target on a sparse A (scs_set_sparse_outputs; opt-in): Y is N x K, x0 = vec(X0) with
+# X0 d x K, loss :softmax_ce / :multi_least_squares as for the dense method above.  With
+# sparse_outputs = true the sparse doors accept A under scs_set_outputs and the products A*X, A'*R read
+# the nonzeros once for all K columns; without it the library refuses, naming the switch.  One device,
+# one rank, the full batch; a sparse Atest takes an Ntest x K ytest.
+function DeviceProblem(A::SparseMatrixCSC{Float64}, Y::AbstractMatrix, x0::Vector{Float64}, loss::Symbol, λ;
+                       sparse_outputs::Bool=false, out_fn::Union{Symbol,Nothing}=nothing,
+                       scale::Float64=1.0 / size(A, 1), L=nothing, sol::Vector{Float64}=zero(x0), C_set=nothing,
+                       P=nothing, device::Integer=0, val_f32::Bool=false, Atest=nothing, ytest=nothing)
+    N, d = size(A)
+    K = size(Y, 2)
+    (size(Y, 1) == N && length(x0) == d * K) ||
+        throw(DimensionMismatch("Y must be N x K and length(x0) = size(A, 2) * K"))
+    ctx = create_ctx(device)
+    chk(ccall((:scs_set_sparse_outputs, lib), Cint, (Ptr{Cvoid}, Cint), ctx, sparse_outputs ? 1 : 0), ctx)
+    chk(ccall((:scs_set_outputs, lib), Cint, (Ptr{Cvoid}, Cint), ctx, K), ctx)
+    Ym = Matrix{Float64}(Y)
+    At = SparseMatrixCSC(transpose(A))
+    rowptr = Int64.(At.colptr .- 1); colidx = Int32.(At.rowval .- 1); val = Vector{Float64}(At.nzval)
+    colptr = Int64.(A.colptr .- 1);  rowidx = Int32.(A.rowval .- 1);  valT = Vector{Float64}(A.nzval)
+    chk(ccall((:scs_set_sparse, lib), Cint,
+              (Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Int64}, Ptr{Int32}, Ptr{Float64}, Ptr{Int64}, Ptr{Int32},
+               Ptr{Float64}, Cint, Ptr{Float64}, Int64, Int64),
+              ctx, N, d, nnz(A), rowptr, colidx, val, colptr, rowidx, valT, val_f32 ? 1 : 0, Ym, N, 0), ctx)
+    model = finish_problem(ctx, A, Ym, x0, loss, λ, out_fn, scale, L, sol, C_set, P)
+    return set_test!(model, Atest, ytest; val_f32)
+end
+
+# ... and from a device CSR (the method above with three device pointers): m is A's column count d, Y a
+# host N x K matrix.
+function DeviceProblem(rowptr::Ptr{Cvoid}, colidx::Ptr{Cvoid}, val::Ptr{Cvoid}, N::Integer, m::Integer,
+                       nnz::Integer, Y::AbstractMatrix, x0::Vector{Float64}, loss::Symbol, λ;
+                       sparse_outputs::Bool=false, ptr_type::Type=Int64, idx_type::Type=Int32, elem::Type=Float64,
+                       val_f32::Bool=false, stream::Ptr{Cvoid}=C_NULL,
+                       out_fn::Union{Symbol,Nothing}=nothing, scale::Float64=1.0 / N,
+                       L=nothing, sol::Vector{Float64}=zero(x0), C_set=nothing, P=nothing, device::Integer=0)
+    K = size(Y, 2)
+    (size(Y, 1) == N && length(x0) == m * K) ||
+        throw(DimensionMismatch("Y must be N x K and length(x0) = m * K"))
+    pb, ib, vb = csr_width(ptr_type), csr_width(idx_type), val_width(elem)
+    ctx = create_ctx(device, nothing, :rccl)
+    chk(ccall((:scs_set_sparse_outputs, lib), Cint, (Ptr{Cvoid}, Cint), ctx, sparse_outputs ? 1 : 0), ctx)
+    chk(ccall((:scs_set_outputs, lib), Cint, (Ptr{Cvoid}, Cint), ctx, K), ctx)
+    Ym = Matrix{Float64}(Y)
+    GC.@preserve Ym chk(ccall((:scs_set_sparse_device, lib), Cint,
+              (Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint, Cint,
+               Ptr{Float64}, Ptr{Cvoid}, Int64, Int64),
+              ctx, N, m, nnz, rowptr, pb, colidx, ib, val, vb, val_f32 ? 1 : 0, pointer(Ym), stream, N, 0), ctx)
+    return finish_problem(ctx, nothing, Ym, x0, loss, λ, out_fn, scale, L, sol, C_set, P)
+end
+
 # CSR held-out rows from device memory (scs_set_test_sparse_device), as the method above takes A
 function set_test_sparse_device!(model::DeviceProblem, rowptr::Ptr{Cvoid}, colidx::Ptr{Cvoid}, val::Ptr{Cvoid},
                                  Ntest::Integer, nnz::Integer, ytest::Union{AbstractVector,Ptr{Cvoid}};

@@ -114,6 +114,7 @@ _SIGS = {
     "scs_comm_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                 C.POINTER(C.c_int), C.c_char_p, C.c_int64]),
     "scs_set_outputs": (C.c_int, [C.c_void_p, C.c_int]),
+    "scs_set_sparse_outputs": (C.c_int, [C.c_void_p, C.c_int]),
     "scs_get_outputs": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), c_i64p]),
     "scs_set_data": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, c_dp, C.c_int64, c_dp, C.c_int64, C.c_int64]),
     "scs_gen_data": (C.c_int, [C.c_void_p, C.POINTER(Synth)]),

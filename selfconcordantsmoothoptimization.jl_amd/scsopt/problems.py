@@ -96,7 +96,7 @@ class Problem:
     def __init__(self, *args, Atest=None, ytest=None, L=None, sol=None, C_set=None, P=None,
                  out_fn: Optional[OutFn] = None, name=None, device=0, comm=None, N_global=None, row0=0,
                  sparse_f32=False, devices=None, device_exchange="rccl", Ntest_global=None, test_row0=0,
-                 dense_f32=False, sparse_batches=False, sparse_sample=False, _ctx=None):
+                 dense_f32=False, sparse_batches=False, sparse_sample=False, sparse_outputs=False, _ctx=None):
         if len(args) == 5:
             A, y, x0, f, lam = args
         elif len(args) == 3:
@@ -120,6 +120,9 @@ class Problem:
         self.generic = A is None and _ctx is None
         # multi-output losses (losses.softmax_ce / multi_least_squares): K = nout outputs on one N x d A,
         # x = vec(X) with X d x K, Y N x K (scs_set_outputs)
+        # sparse_outputs: a multi-output loss on a sparse A (scipy matrix or device CSR) -- the products run
+        # with nout right-hand sides in one pass over the nonzeros (scs_set_sparse_outputs)
+        self.sparse_outputs = bool(sparse_outputs)
         self.nout = self._check_outputs(f, out_fn, A, comm, devices, _ctx)
         self.d = self.m // self.nout   # A's columns
         if f.kind == "callback":   # the data stays with the caller's closures; the device holds none
@@ -144,6 +147,8 @@ class Problem:
             self.ctx.check(_lib.lib.scs_set_sparse_batches(self.ctx.h, 1))
         if sparse_sample:
             self.ctx.check(_lib.lib.scs_set_sparse_sample(self.ctx.h, 1))
+        if self.sparse_outputs:   # a mode of the context: inert without nout
+            self.ctx.check(_lib.lib.scs_set_sparse_outputs(self.ctx.h, 1))
         if self.nout > 1:   # before the data door: its m is then A's column count d, y is N x nout
             self.ctx.check(_lib.lib.scs_set_outputs(self.ctx.h, self.nout))
         if comm is not None and comm.active and _ctx is None:
@@ -245,8 +250,9 @@ class Problem:
             self.ctx.check(_lib.lib.scs_set_test_callback(self.ctx.h, 1))
             self.test_model = True
             return
-        if self.nout > 1 and _lib.is_device_csr(Atest):
-            raise ValueError("a sparse Atest is not supported with nout (multi-output losses take dense rows)")
+        if self.nout > 1 and _lib.is_device_csr(Atest) and not self.sparse_outputs:
+            raise ValueError("a sparse Atest is not supported with nout (multi-output losses take dense rows); "
+                             "pass sparse_outputs=True / scs_set_sparse_outputs")
         if _lib.is_device_csr(Atest):
             if len(self.ctx.devices) > 1:
                 raise ValueError("a devices=[...] problem takes host held-out rows, not a device CSR")
@@ -259,18 +265,25 @@ class Problem:
             self._set_device(Atest, ytest, True, Ntest_global, row0)
             self.test_model = True
             return
-        if self.nout > 1:
+        if self.nout > 1 and not (_is_sparse(Atest) and self.sparse_outputs):
             if _is_sparse(Atest):
-                raise ValueError("a sparse Atest is not supported with nout (multi-output losses take dense rows)")
+                raise ValueError("a sparse Atest is not supported with nout (multi-output losses take dense rows); "
+                                 "pass sparse_outputs=True / scs_set_sparse_outputs")
             self._set_host_multi(Atest, ytest, True)
             self.test_model = True
             return
-        yv = np.ascontiguousarray(np.asarray(ytest, dtype=np.float64).reshape(-1))
+        if self.nout > 1:   # Ntest x nout targets, column-major
+            _yp, yv = self._targets(ytest, int(Atest.shape[0]))
+            if yv is None:
+                raise ValueError("a host sparse Atest takes host targets")
+            yv = yv.reshape(-1, order="F")
+        else:
+            yv = np.ascontiguousarray(np.asarray(ytest, dtype=np.float64).reshape(-1))
         Ng = int(Ntest_global) if Ntest_global is not None else 0
         if _is_sparse(Atest):
             csr = Atest.tocsr()
-            if csr.shape[1] != self.m or csr.shape[0] != yv.shape[0]:
-                raise ValueError(f"Atest must be Ntest x m (m = {self.m}) with len(ytest) = Ntest")
+            if csr.shape[1] != self.d or csr.shape[0] * self.nout != yv.shape[0]:
+                raise ValueError(f"Atest must be Ntest x m (m = {self.d}) with len(ytest) = Ntest")
             rowptr = np.ascontiguousarray(csr.indptr, dtype=np.int64)
             colidx = np.ascontiguousarray(csr.indices, dtype=np.int32)
             val = np.ascontiguousarray(csr.data, dtype=np.float64)
@@ -310,8 +323,9 @@ class Problem:
             raise ValueError(f"nout = {k} is outside 2..16")
         if A is None or _ctx is not None:
             raise ValueError("a multi-output loss (nout) needs a dense A: Problem(A, Y, x0, f, λ)")
-        if _lib.is_device_csr(A) or _is_sparse(A):
-            raise ValueError("a sparse A is not supported with nout (multi-output losses take a dense A)")
+        if (_lib.is_device_csr(A) or _is_sparse(A)) and not self.sparse_outputs:
+            raise ValueError("a sparse A is not supported with nout (multi-output losses take a dense A); "
+                             "pass sparse_outputs=True / scs_set_sparse_outputs")
         if devices is not None:
             raise ValueError("devices=[...] is not supported with nout (multi-output losses run on one device)")
         if comm is not None and comm.active:
@@ -418,8 +432,9 @@ class Problem:
         entries are taken as scipy's tocsr() / tocsc() keep them.  Returns N."""
         shape, indptr, indices, data = _lib.device_csr_arrays(A)
         d = _lib.parse_device_csr(shape, *(a.__cuda_array_interface__ for a in (indptr, indices, data)))
-        if d["m"] != self.m:
-            raise ValueError(f"A must be N x m with m = length(x0) = {self.m}")
+        if d["m"] * self.nout != self.m:
+            raise ValueError(f"A must be N x m with m = length(x0) = {self.m}" if self.nout == 1 else
+                             f"A must be N x d with d * nout = length(x0) = {self.m} (nout = {self.nout})")
         N = d["N"]
         yp, stream, _keep = self._device_y_and_stream((indptr, indices, data), y, N, d["stream"])
         Ng = 0 if N_global is None else int(N_global)
@@ -428,7 +443,7 @@ class Problem:
         if test:
             rc = _lib.lib.scs_set_test_sparse_device(self.ctx.h, N, d["nnz"], *src, Ng, int(row0))
         else:
-            rc = _lib.lib.scs_set_sparse_device(self.ctx.h, N, self.m, d["nnz"], *src, Ng if Ng else N, int(row0))
+            rc = _lib.lib.scs_set_sparse_device(self.ctx.h, N, self.d, d["nnz"], *src, Ng if Ng else N, int(row0))
         self.ctx.check(rc)
         return N
 
@@ -643,8 +658,9 @@ class Problem:
     def _set_sparse(self, A, y, N_global, row0, f32):
         csr = A.tocsr()
         csc = A.tocsc()
-        if csr.shape[1] != self.m:
-            raise ValueError(f"A must be N x m with m = length(x0) = {self.m}")
+        if csr.shape[1] * self.nout != self.m:
+            raise ValueError(f"A must be N x m with m = length(x0) = {self.m}" if self.nout == 1 else
+                             f"A must be N x d with d * nout = length(x0) = {self.m} (nout = {self.nout})")
         self.N = int(csr.shape[0])
         rowptr = np.ascontiguousarray(csr.indptr, dtype=np.int64)
         colidx = np.ascontiguousarray(csr.indices, dtype=np.int32)
@@ -652,11 +668,17 @@ class Problem:
         colptr = np.ascontiguousarray(csc.indptr, dtype=np.int64)
         rowidx = np.ascontiguousarray(csc.indices, dtype=np.int32)
         valT = np.ascontiguousarray(csc.data, dtype=np.float64)
-        yv = np.ascontiguousarray(np.asarray(y, dtype=np.float64).reshape(-1))
+        if self.nout > 1:   # N x nout targets, column-major
+            _yp, yv = self._targets(y, self.N)
+            if yv is None:
+                raise ValueError("a host sparse A takes host targets (a device CSR takes either)")
+            yv = yv.reshape(-1, order="F")
+        else:
+            yv = np.ascontiguousarray(np.asarray(y, dtype=np.float64).reshape(-1))
         Ng = self.N if N_global is None else int(N_global)
         i64, i32 = _lib.c_i64p, _lib.c_i32p
         self.ctx.check(_lib.lib.scs_set_sparse(
-            self.ctx.h, self.N, self.m, int(val.shape[0]), rowptr.ctypes.data_as(i64), colidx.ctypes.data_as(i32),
+            self.ctx.h, self.N, self.d, int(val.shape[0]), rowptr.ctypes.data_as(i64), colidx.ctypes.data_as(i32),
             dptr(val), colptr.ctypes.data_as(i64), rowidx.ctypes.data_as(i32), dptr(valT), 1 if f32 else 0,
             dptr(yv), Ng, int(row0)))
 
@@ -675,21 +697,23 @@ class Problem:
         val = np.zeros(max(nnz, 1), dtype=np.float64)
         self.ctx.check(_lib.lib.scs_get_sparse(self.ctx.h, rowptr.ctypes.data_as(_lib.c_i64p),
                                                colidx.ctypes.data_as(_lib.c_i32p), dptr(val)))
-        y = np.zeros(self.N, dtype=np.float64)
+        y = np.zeros(self.N * self.nout, dtype=np.float64)   # (multi-output: N x nout, column-major)
         self.ctx.check(_lib.lib.scs_get_data(self.ctx.h, 0, self.N, None, self.N, dptr(y)))
-        return sp.csr_matrix((val[:nnz], colidx[:nnz], rowptr), shape=(self.N, self.m)), y
+        if self.nout > 1:
+            y = np.ascontiguousarray(y.reshape(self.nout, self.N).T)
+        return sp.csr_matrix((val[:nnz], colidx[:nnz], rowptr), shape=(self.N, self.d)), y
 
     def get_sparse_csc(self):
         """The device CSC copy of A as a scipy.sparse.csc_matrix (values widened to fp64), entries as
         the device holds them: rows ascending within a column, duplicates kept."""
         import scipy.sparse as sp
         nnz = self.nnz
-        colptr = np.zeros(self.m + 1, dtype=np.int64)
+        colptr = np.zeros(self.d + 1, dtype=np.int64)
         rowidx = np.zeros(max(nnz, 1), dtype=np.int32)
         valT = np.zeros(max(nnz, 1), dtype=np.float64)
         self.ctx.check(_lib.lib.scs_get_sparse_csc(self.ctx.h, colptr.ctypes.data_as(_lib.c_i64p),
                                                    rowidx.ctypes.data_as(_lib.c_i32p), dptr(valT)))
-        return sp.csc_matrix((valT[:nnz], rowidx[:nnz], colptr), shape=(self.N, self.m))
+        return sp.csc_matrix((valT[:nnz], rowidx[:nnz], colptr), shape=(self.N, self.d))
 
     # device evaluation helpers ------------------------------------------------
     def fx(self, x):
