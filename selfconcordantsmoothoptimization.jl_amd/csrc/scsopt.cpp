@@ -38,6 +38,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "batch_plan.h"
+#include "data_view.h"
 #include "shard_plan.h"
 
 using namespace scs;
@@ -60,62 +61,11 @@ struct DevBuf {
   size_t bytes = 0;
 };
 
-// The N-dependent state of a context: the data rows with their sample-space workspace and the
-// GGN sample-space caches.  A minibatch (scs_set_batch) is a second view swapped in for the
-// duration of scs_step (the As, ys handed to step!, iterate.jl:205-207).
-// an LDS-blocked copy of a sparse A (sparse.hip)
-struct SpBlkT {
-  int shift = 0, nblk = 0;
-  // blocks per partial: 1 in the single-vector layout; the K-column layout of a multi-output context
-  // (scs_set_sparse_outputs, multi_sparse.hip) cuts each 16384-index block into kp sub-blocks and the
-  // products still write one partial per group of kp
-  int kp = 1;
-  int64_t nnz = 0;   // entries of the copy
-  int64_t* ptr = nullptr;
-  uint16_t* lidx = nullptr;
-  void* val = nullptr;
-};
-
-struct NView {
-  double* A = nullptr;
-  int a32 = 0;   // A holds float elements (scs_set_dense_f32): half the doubles allocated, widened on load
-  double* y = nullptr;
-  int64_t N = 0, Npad = 0, nstage = 0, Nglob = 0;
-  int nsplit = 1, nval = 1, nchunk = 1;
-  double *zpart = nullptr, *z = nullptr, *gN = nullptr, *hN = nullptr, *wN = nullptr, *vN = nullptr,
-         *valpart = nullptr, *tpart = nullptr;
-  double *At = nullptr, *Ps = nullptr, *Ms = nullptr, *bS = nullptr, *uN = nullptr, *hvec = nullptr, *hg = nullptr;
-  int64_t NpS = 0;
-  int2* stiles = nullptr;
-  int nstiles = 0;
-  int64_t n1pad = 0;     // row stride of Ms: round_up(N + 1, 128) (lu.hip)
-  bool sparse = false;   // a batch view is dense (Matrix(As'), iterate.jl:207) unless spv is set
-  // a sparse batch view (scs_set_sparse_batches): the batch's entry count and the two blocked copies
-  // scs_set_sparse would build from A[rows_b, :], exchanged with the context's by swap_view.  spv
-  // stays with the view object (it is not swapped).
-  bool spv = false;
-  int64_t nnz = 0;
-  SpBlkT bcsr, bcsc;
-  // ... which also serves ProxGGNSCORE's sample-space branch (scs_set_sparse_sample, ssv): the batch's
-  // plain CSR and the Gram-blocked copy of its CSC, exchanged with the context's rowptr / colidx / val
-  // and sgram.  The (n+1)² system scratch is not the view's: sample_sys keeps one set per size.
-  bool ssv = false;
-  int64_t* rowptr = nullptr;
-  int* colidx = nullptr;
-  void* val = nullptr;
-  SpBlkT sgram;
-};
-
-// the per-step scratch of the sparse sample-space branch for n samples: P, the (n+1)² system and its
-// vectors (2·n² doubles), shared by the full data or every batch view of that size
-struct SampleSys {
-  int64_t N = -1, NpS = 0, n1pad = 0;
-  double *Ps = nullptr, *Ms = nullptr, *bS = nullptr, *uN = nullptr, *hvec = nullptr, *hg = nullptr;
-};
-
 }  // namespace
 
-struct scs_ctx {
+// the data view in place is the ViewData base (data_view.h): the full data, or the view swapped in for
+// the duration of a call
+struct scs_ctx : ViewData {
   int dev = 0;
   hipStream_t st = nullptr;
   bool own_stream = false;
@@ -133,7 +83,7 @@ struct scs_ctx {
   bool own_red = false;   // red allocated by the library (no scs_set_reduce_buffer)
 
   // data
-  int64_t N = 0, Npad = 0, m = 0, mpad = 0, Nglob = 0, row0 = 0;
+  int64_t m = 0, mpad = 0, row0 = 0;
   // multi-output targets (scs_set_outputs): nout = K outputs share one dense A of dc columns (dcp: padded
   // to whole panels); the variable count is m = dc·K.  nout = 0 (unset): dc = m, dcp = mpad.  The data
   // view's column count (dc, dcp) serves the products, the Gram, the tile lists and the doors; m, mpad
@@ -151,33 +101,23 @@ struct scs_ctx {
   int64_t mVt_cap = 0;
   double* Gd = nullptr;    // one dc x dc weighted Gram (dcp²) before its placement into G
   int64_t Nglob_data = 0;   // N_global of the full data (Nglob follows the swapped-in view)
-  int64_t nstage = 0;  // Npad / 16: stages of the panel-blocked A (common.h tiled_off)
   bool has_data = false;
   bool generic = false;  // ProblemGeneric (no A)
-  double* A = nullptr;
   // fp32 storage of the dense row blocks (scs_set_dense_f32): a32 says what A holds now (it follows the
   // swapped-in view), dense_f32 is the mode of the blocks uploaded or generated next; the arithmetic
   // stays fp64 (f32c below is independent of both)
-  int a32 = 0, dense_f32 = 0;
-  double* y = nullptr;
-  // sparse A: CSR (rows) + CSC copy (columns), values fp64 or fp32
-  bool sparse = false;
-  int sp_f32 = 0;
+  int dense_f32 = 0;
+  // sparse A: the view's CSR (rows) + the CSC copy (columns) of the full data, values fp64 or fp32
   // scs_set_compute_f32: fp32 ARITHMETIC in the sparse products (fp32-stored values) and the L-BFGS
   // two-loop -- the compute arm of BASELINE configs[4]'s fp32-vs-fp64 study; 0 (fp64) by default
   int f32c = 0;
-  int64_t nnz = 0;
-  int64_t *rowptr = nullptr, *colptr = nullptr;
-  int *colidx = nullptr, *rowidx = nullptr;
-  void *val = nullptr, *valT = nullptr;
-  using SpBlk = SpBlkT;
-  SpBlk bcsr, bcsc;  // LDS-blocked copies used by the products (sparse.hip)
-  SpBlk bgram;    // the sparse Gram's row copy: 2^sparse_gram_shift()-wide blocks, unpadded (built on first use)
-  // scs_set_sparse_sample: ProxGGNSCORE's sample-space P = A diag(h) Aᵀ of a sparse A from its nonzeros.
-  // sgram: the Gram-blocked copy of the CSC (columns cut into 2^sparse_gram_shift()-wide blocks of
-  // rows, unpadded; built on first use, a batch view brings its own); ssys: the system scratch per size
+  int64_t* colptr = nullptr;
+  int* rowidx = nullptr;
+  void* valT = nullptr;
+  SpBlkT bgram;   // the sparse Gram's row copy: 2^sparse_gram_shift()-wide blocks, unpadded (built on first use)
+  // scs_set_sparse_sample: ProxGGNSCORE's sample-space P = A diag(h) Aᵀ of a sparse A from its nonzeros
+  // (the view's sgram); ssys: the system scratch per size
   int sparse_sample = 0;
-  SpBlk sgram;
   std::vector<SampleSys> ssys;
   struct SegGram {   // the sparse Gram's variant-8 structure (build_gram_seg, on first use)
     int state = 0;   // 0 not tried, 1 built, -1 not built (memory / size): the Gram-blocked walk instead
@@ -281,13 +221,6 @@ struct scs_ctx {
   double* hloop_dev = nullptr;   // its device-side address
   hipEvent_t loop_ev[2] = {nullptr, nullptr};
   bool dev_loop = false;    // scs_iterate's device-resident loop: steps leave x_new / pri on the device
-  // N-space workspace
-  int nsplit = 1;
-  double *zpart = nullptr, *z = nullptr, *gN = nullptr, *hN = nullptr, *wN = nullptr, *vN = nullptr,
-         *valpart = nullptr;
-  int nval = 1;
-  int nchunk = 1;
-  double* tpart = nullptr;
   // Gram / solve
   double *G = nullptr, *Gc = nullptr;
   int2* tiles = nullptr;    // Gram launch list
@@ -356,12 +289,6 @@ struct scs_ctx {
   double *qeS = nullptr, *qeA = nullptr, *qeb = nullptr, *qebk = nullptr;
   QRAux qre;
   int64_t qe_np = 0, qebk_n = 0;
-  // GGN sample-space branch (N + 1 <= m): Aᵀ copy, sample Gram, (N+1)² system
-  double *At = nullptr, *Ps = nullptr, *Ms = nullptr, *bS = nullptr, *uN = nullptr, *hvec = nullptr, *hg = nullptr;
-  int64_t NpS = 0;
-  int2* stiles = nullptr;
-  int nstiles = 0;
-  int64_t n1pad = 0;
   // minibatches (scs_set_batches / scs_select_batch): the collected DataLoader batch list of
   // iterate.jl:141-146 as one device row list; each distinct batch size owns a gathered view
   // (NView) that is swapped in for the steps on that batch
@@ -389,8 +316,8 @@ struct scs_ctx {
   // all ranks' rows of the full data or of the selected batch (GGN sample-space branch with
   // N_global + 1 <= m on several ranks)
   NView gview;
-  // held-out data (Problem(...; Atest, ytest), problems.jl:27-28,67-68): a view of its own (rows, y,
-  // the f workspace; a sparse set also its CSR + LDS-blocked copy) swapped in only to evaluate
+  // held-out data (Problem(...; Atest, ytest), problems.jl:27-28,67-68): a view of its own (VIEW_TEST: rows,
+  // y, the f workspace; a sparse set also its CSR + LDS-blocked copy) swapped in only to evaluate
   // ftest(x) = f(Atest, ytest, x) at the loop's stats pushes (iterate.jl:169-175, utils.jl:55-57).
   // `host`: a callback loss evaluates it on the caller's side (SCS_CB_FTEST)
   struct TestSet {
@@ -400,12 +327,7 @@ struct scs_ctx {
     // `ftest` unassigned (iterate.jl:170-171), so its first show_stat! call (:201) raises
     // UndefVarError -- scs_iterate fails the same way at its first stats push
     bool xor_case = false;
-    int sp_f32 = 0;
-    int64_t nnz = 0;
-    SpBlk bcsr;
-    int64_t* rowptr = nullptr;
-    int* colidx = nullptr;
-    void* val = nullptr;
+    TestSet() { v.parts = VIEW_TEST; }
   } tset;
   bool gview_ok = false;
   int64_t gview_batch = -1;    // the batch gview holds (-1: the full data) ...
@@ -784,29 +706,37 @@ void alloc_mspace(scs_ctx* c) {
   }
 }
 
-void alloc_nspace(scs_ctx* c) {
-  if (c->generic) return;
+// free the device buffers of v's groups (data_view.h VB_*)
+void free_buffers(scs_ctx* c, ViewData& v, unsigned groups) {
+  view_buffers(v, groups, [c](auto*& p) { dfree_t(c, p); });
+}
+
+void free_blk(scs_ctx* c, SpBlkT& B) {
+  blk_buffers(B, [c](auto*& p) { dfree_t(c, p); });
+  B = SpBlkT();
+}
+
+// the N-space workspace of v, sized by its rows (a sparse v: by its blocked copies; a sparse held-out
+// view brings no column copy and is sized by `bcsc`, the data's)
+void alloc_nspace(scs_ctx* c, ViewData& v, const SpBlkT& bcsc) {
   ++c->y_stamp;   // a new view: its y is (re)written by the caller of this function
   const int64_t K = kout(c);   // multi-output: Z, R, P are N x K (stride Npad), the partials K columns per slice
-  c->nsplit = c->sparse ? blk_groups(c->bcsr) : gemv_n_splits(c->Npad, c->dc);
-  c->nval = epilogue_blocks(c->Npad);
-  c->nchunk = c->sparse ? blk_groups(c->bcsc) : multi(c) ? multi_atv_chunks(c->Npad) : gemv_t_chunks(c->Npad);
-  dfree_t(c, c->zpart);
-  dfree_t(c, c->z);
-  dfree_t(c, c->gN);
-  dfree_t(c, c->hN);
-  dfree_t(c, c->wN);
-  dfree_t(c, c->vN);
-  dfree_t(c, c->valpart);
-  dfree_t(c, c->tpart);
-  c->zpart = dalloc<double>(c, (size_t)c->nsplit * c->Npad * K);
-  c->z = dalloc<double>(c, c->Npad * K);
-  c->gN = dalloc<double>(c, c->Npad * K);
-  c->hN = dalloc<double>(c, c->Npad * K);
-  c->wN = dalloc<double>(c, c->Npad);
-  c->vN = dalloc<double>(c, c->Npad);
-  c->valpart = dalloc<double>(c, c->nval);
-  c->tpart = dalloc<double>(c, (size_t)c->nchunk * (multi(c) ? c->dcp * K : c->mpad));
+  v.nsplit = v.sparse ? blk_groups(v.bcsr) : gemv_n_splits(v.Npad, c->dc);
+  v.nval = epilogue_blocks(v.Npad);
+  v.nchunk = v.sparse ? blk_groups(bcsc) : multi(c) ? multi_atv_chunks(v.Npad) : gemv_t_chunks(v.Npad);
+  free_buffers(c, v, VB_WORK);
+  v.zpart = dalloc<double>(c, (size_t)v.nsplit * v.Npad * K);
+  v.z = dalloc<double>(c, v.Npad * K);
+  v.gN = dalloc<double>(c, v.Npad * K);
+  v.hN = dalloc<double>(c, v.Npad * K);
+  v.wN = dalloc<double>(c, v.Npad);
+  v.vN = dalloc<double>(c, v.Npad);
+  v.valpart = dalloc<double>(c, v.nval);
+  v.tpart = dalloc<double>(c, (size_t)v.nchunk * (multi(c) ? c->dcp * K : c->mpad));
+}
+void alloc_nspace(scs_ctx* c, ViewData& v) { alloc_nspace(c, v, v.bcsc); }
+void alloc_nspace(scs_ctx* c) {   // the view in place
+  if (!c->generic) alloc_nspace(c, *c);
 }
 
 void ensure_gram(scs_ctx* c) {
@@ -1017,61 +947,18 @@ double* alloc_A(scs_ctx* c, int64_t rows, int a32, bool zero = true) {
 // exchange the context's N-dependent fields with v (the full data <-> a minibatch)
 void swap_view(scs_ctx* c, NView& v) {
   ++c->data_gen;
-  std::swap(c->sparse, v.sparse);
-  std::swap(c->A, v.A);
-  std::swap(c->a32, v.a32);
-  std::swap(c->y, v.y);
-  std::swap(c->N, v.N);
-  std::swap(c->Npad, v.Npad);
-  std::swap(c->nstage, v.nstage);
-  std::swap(c->Nglob, v.Nglob);
-  std::swap(c->nsplit, v.nsplit);
-  std::swap(c->nval, v.nval);
-  std::swap(c->nchunk, v.nchunk);
-  for (auto pr : {std::make_pair(&c->zpart, &v.zpart), std::make_pair(&c->z, &v.z), std::make_pair(&c->gN, &v.gN),
-                  std::make_pair(&c->hN, &v.hN), std::make_pair(&c->wN, &v.wN), std::make_pair(&c->vN, &v.vN),
-                  std::make_pair(&c->valpart, &v.valpart), std::make_pair(&c->tpart, &v.tpart),
-                  std::make_pair(&c->At, &v.At), std::make_pair(&c->Ps, &v.Ps), std::make_pair(&c->Ms, &v.Ms),
-                  std::make_pair(&c->bS, &v.bS), std::make_pair(&c->uN, &v.uN), std::make_pair(&c->hvec, &v.hvec),
-                  std::make_pair(&c->hg, &v.hg)})
-    std::swap(*pr.first, *pr.second);
-  std::swap(c->NpS, v.NpS);
-  std::swap(c->stiles, v.stiles);
-  std::swap(c->nstiles, v.nstiles);
-  std::swap(c->n1pad, v.n1pad);
-  if (v.spv) {   // a sparse batch view: the products' blocked copies go with it (sp_f32 is the data's)
-    std::swap(c->nnz, v.nnz);
-    std::swap(c->bcsr, v.bcsr);
-    std::swap(c->bcsc, v.bcsc);
-  }
-  if (v.ssv) {
-    std::swap(c->rowptr, v.rowptr);
-    std::swap(c->colidx, v.colidx);
-    std::swap(c->val, v.val);
-    std::swap(c->sgram, v.sgram);
-  }
+  swap_view_data(*c, v, v.parts);
 }
 
+// give v's buffers back and reset its fields (what it carries, v.parts, stays)
 void free_view(scs_ctx* c, NView& v) {
   ++c->y_stamp;   // a later allocation may reuse y's address
-  for (double** p : {&v.A, &v.y, &v.zpart, &v.z, &v.gN, &v.hN, &v.wN, &v.vN, &v.valpart, &v.tpart, &v.At, &v.Ps,
-                     &v.Ms, &v.bS, &v.uN, &v.hvec, &v.hg})
-    dfree_t(c, *p);
-  dfree_t(c, v.stiles);
-  for (SpBlkT* B : {&v.bcsr, &v.bcsc, &v.sgram}) {
-    dfree_t(c, B->ptr);
-    dfree_t(c, B->lidx);
-    dfree(c, B->val);
-  }
-  dfree_t(c, v.rowptr);
-  dfree_t(c, v.colidx);
-  dfree(c, v.val);
-  v = NView();
+  free_buffers(c, v, VB_ALL);
+  static_cast<ViewData&>(v) = ViewData();
 }
 
 void free_sample_sys(scs_ctx* c) {
-  for (SampleSys& S : c->ssys)
-    for (double** p : {&S.Ps, &S.Ms, &S.bS, &S.uN, &S.hvec, &S.hg}) dfree_t(c, *p);
+  for (SampleSys& S : c->ssys) sys_buffers(S, [c](auto*& p) { dfree_t(c, p); });
   c->ssys.clear();
 }
 
@@ -1088,16 +975,9 @@ int batch_view_kind(const scs_ctx* c, int method) {
 // workspace and, for a sparse set, the CSR arrays and the SpMV's blocked copy).  Not a data
 // change: the data generation (the Gram cache's key) and the product kernel name are kept.
 void swap_test(scs_ctx* c) {
-  auto& t = c->tset;
   const uint64_t gen = c->data_gen;
-  swap_view(c, t.v);
+  swap_view(c, c->tset.v);
   c->data_gen = gen;
-  std::swap(c->sp_f32, t.sp_f32);
-  std::swap(c->nnz, t.nnz);
-  std::swap(c->bcsr, t.bcsr);
-  std::swap(c->rowptr, t.rowptr);
-  std::swap(c->colidx, t.colidx);
-  std::swap(c->val, t.val);
 }
 
 struct TestScope {
@@ -1113,15 +993,6 @@ struct TestScope {
 void free_test(scs_ctx* c) {
   auto& t = c->tset;
   free_view(c, t.v);
-  dfree_t(c, t.bcsr.ptr);
-  dfree_t(c, t.bcsr.lidx);
-  dfree(c, t.bcsr.val);
-  t.bcsr = scs_ctx::SpBlk();
-  dfree_t(c, t.rowptr);
-  dfree_t(c, t.colidx);
-  dfree(c, t.val);
-  t.nnz = 0;
-  t.sp_f32 = 0;
   t.on = t.host = t.xor_case = false;
 }
 
@@ -1167,7 +1038,6 @@ void clear_batches(scs_ctx* c) {
   ++c->batch_gen;
   if (c->gview_ok && c->gview_batch >= 0) {
     free_view(c, c->gview);
-    c->gview = NView();
     c->gview_ok = false;
   }
   free_dense_views(c);
@@ -1194,13 +1064,7 @@ size_t alloc_bytes(const scs_ctx* c, const void* p) {
 // the GGN sample space: also its plain CSR and the Gram-blocked column copy)
 int64_t sparse_view_bytes(const scs_ctx* c, const NView& v) {
   size_t t = 0;
-  for (const void* p : {(const void*)v.y, (const void*)v.zpart, (const void*)v.z, (const void*)v.gN,
-                        (const void*)v.hN, (const void*)v.wN, (const void*)v.vN, (const void*)v.valpart,
-                        (const void*)v.tpart, (const void*)v.bcsr.ptr, (const void*)v.bcsr.lidx,
-                        (const void*)v.bcsr.val, (const void*)v.bcsc.ptr, (const void*)v.bcsc.lidx,
-                        (const void*)v.bcsc.val, (const void*)v.rowptr, (const void*)v.colidx, (const void*)v.val,
-                        (const void*)v.sgram.ptr, (const void*)v.sgram.lidx, (const void*)v.sgram.val})
-    t += alloc_bytes(c, p);
+  view_buffers(v, VB_SPARSE_VIEW, [&](const void* p) { t += alloc_bytes(c, p); });
   return (int64_t)t;
 }
 
@@ -1251,8 +1115,7 @@ int build_sparse_view(scs_ctx* c, int64_t b, bool ssv) {
   const size_t vs = f32 ? sizeof(float) : sizeof(double);
   const SpBlkT& F = c->bcsr;
   NView v;
-  v.spv = true;
-  v.ssv = ssv;
+  v.parts = ssv ? VIEW_SPARSE_SAMPLE : VIEW_SPARSE;
   v.sparse = true;
   v.N = n;
   v.Nglob = ng;
@@ -1260,7 +1123,7 @@ int build_sparse_view(scs_ctx* c, int64_t b, bool ssv) {
   // products launch nothing and its zero partials add nothing to the exchanged sums)
   v.Npad = round_up(std::max<int64_t>(n, 1), 16);
   v.nstage = v.Npad / 16;
-  SpBlkT R, Cc;
+  SpBlkT &R = v.bcsr, &Cc = v.bcsc;   // owned by v from the start: free_view gives a failed build's arrays back
   R.shift = F.shift;
   R.nblk = F.nblk;
   Cc.shift = spmv_blk_shift(n);
@@ -1270,7 +1133,7 @@ int build_sparse_view(scs_ctx* c, int64_t b, bool ssv) {
   int64_t *ptrR = nullptr, *ptrC = nullptr, *colptr_b = nullptr, *bfirst = nullptr;
   int* rowidx_s = nullptr;
   void* valT_s = nullptr;
-  SpBlkT& Gb = v.sgram;   // (ssv) owned by v from the start: free_view gives a failed build's arrays back
+  SpBlkT& Gb = v.sgram;   // (ssv)
   Gb.shift = sparse_gram_shift();
   Gb.nblk = (int)std::max<int64_t>(ceil_div(n, int64_t(1) << Gb.shift), 1);
   const int64_t nkG = (int64_t)Gb.nblk * m;
@@ -1365,15 +1228,11 @@ int build_sparse_view(scs_ctx* c, int64_t b, bool ssv) {
   struct Guard {   // a failed build leaves no half-made view behind
     scs_ctx* c;
     NView* v;
-    SpBlkT *R, *Cc;
     bool done = false;
     ~Guard() {
-      if (done) return;
-      v->bcsr = *R;
-      v->bcsc = *Cc;
-      free_view(c, *v);
+      if (!done) free_view(c, *v);
     }
-  } guard{c, &v, &R, &Cc};
+  } guard{c, &v};
   const int pad = spmv_pad_index();
   R.ptr = dalloc<int64_t>(c, nR, n == 0);
   R.lidx = dalloc<uint16_t>(c, nnzpR + 8, false);
@@ -1417,19 +1276,7 @@ int build_sparse_view(scs_ctx* c, int64_t b, bool ssv) {
     Gb = SpBlkT();
   }
   v.nnz = nnzb;
-  v.bcsr = R;
-  v.bcsc = Cc;
-  R = Cc = SpBlkT();   // owned by v from here
-  swap_view(c, v);     // the workspace follows the view's nblk (nsplit / nchunk)
-  try {
-    alloc_nspace(c);
-  } catch (...) {
-    swap_view(c, v);
-    R = v.bcsr;
-    Cc = v.bcsc;
-    throw;
-  }
-  swap_view(c, v);
+  alloc_nspace(c, v);   // the workspace follows the view's nblk (nsplit / nchunk)
   sync(c);
   guard.done = true;
   bool fresh = false;
@@ -1479,9 +1326,7 @@ void select_batch(scs_ctx* c, int64_t b) {
     v.a32 = c->sparse ? 0 : c->a32;   // a batch of an fp32-stored A is fp32; the dense batch of a sparse A fp64
     v.A = alloc_A(c, v.Npad, v.a32);
     v.y = dalloc<double>(c, v.Npad);
-    swap_view(c, v);
-    alloc_nspace(c);
-    swap_view(c, v);
+    alloc_nspace(c, v);
     c->bpool.push_back(v);
     c->bheld.push_back(-1);
     k = (int)c->bpool.size() - 1;
@@ -1501,7 +1346,7 @@ void select_batch(scs_ctx* c, int64_t b) {
                              c->st));
     }
     // the view's GGN sample-space Aᵀ copy (built once per A, ggn_sample_step) follows its rows
-    if (v.At) HCK(launch_transpose(v.A, v.a32, v.Npad, n, c->m, v.At, c->mpad, v.NpS, c->st));
+    if (v.At) HCK(launch_transpose(v.A, v.a32, v.Npad, n, c->m, v.At, c->mpad, v.ss.NpS, c->st));
     c->bheld[k] = b;
   }
   c->bview = k;
@@ -2324,7 +2169,7 @@ const double* dense_A(scs_ctx* c) {
 // The sparse Gram's row copy: the (sorted) CSR cut into 2^sparse_gram_shift()-wide column blocks,
 // unpadded (blk_count / blk_scan / blk_scatter with no slot rounding).
 void build_gram_blocked(scs_ctx* c) {
-  scs_ctx::SpBlk& B = c->bgram;
+  SpBlkT& B = c->bgram;
   const int64_t nrows = c->N;
   B.shift = sparse_gram_shift();
   B.nblk = (int)ceil_div(c->dc, int64_t(1) << B.shift);
@@ -2709,7 +2554,6 @@ void ggn_sample_direction_sharded(scs_ctx* c, const double* xh) {
   const bool held = c->gview_ok && c->gview_batch == c->bsel && c->gview_gen == gen;
   if (c->gview_ok && !held && c->gview.N != Ng) {   // another size: new buffers
     free_view(c, c->gview);
-    c->gview = NView();
     c->gview_ok = false;
   }
   if (!held) {
@@ -2741,14 +2585,10 @@ void ggn_sample_direction_sharded(scs_ctx* c, const double* xh) {
     HCK(hipMemcpyAsync(v.A, c->red, sizeof(double) * Npg * c->mpad, hipMemcpyDeviceToDevice, c->st));
     HCK(hipMemcpyAsync(v.y, c->red + Npg * c->mpad, sizeof(double) * Npg, hipMemcpyDeviceToDevice, c->st));
     // a refilled view's Aᵀ copy (built once per A by ggn_sample_direction) follows its rows
-    if (!fresh && v.At) HCK(launch_transpose(v.A, 0, v.Npad, Ng, c->m, v.At, c->mpad, v.NpS, c->st));
+    if (!fresh && v.At) HCK(launch_transpose(v.A, 0, v.Npad, Ng, c->m, v.At, c->mpad, v.ss.NpS, c->st));
     sync(c);
     dfree_t(c, drows);
-    if (fresh) {
-      swap_view(c, v);
-      alloc_nspace(c);
-      swap_view(c, v);
-    }
+    if (fresh) alloc_nspace(c, v);
     c->gview_ok = true;
     c->gview_batch = c->bsel;
     c->gview_gen = gen;
@@ -2796,7 +2636,7 @@ SampleSys& sample_sys(scs_ctx* c, int64_t N) {
 // The Gram-blocked copy of the CSC (the column side of build_gram_blocked): the sorted columns cut
 // into 2^sparse_gram_shift()-wide blocks of rows, unpadded.  A batch view brings its own.
 void build_sample_blocked(scs_ctx* c) {
-  scs_ctx::SpBlk& B = c->sgram;
+  SpBlkT& B = c->sgram;
   const int64_t ncols = c->m;
   B.shift = sparse_gram_shift();
   B.nblk = (int)std::max<int64_t>(ceil_div(c->N, int64_t(1) << B.shift), 1);
@@ -2828,12 +2668,10 @@ void sparse_sample_gram(scs_ctx* c, const double* h, double* Ps, int64_t NpS) {
   if (c->spview >= 0 && !c->sgram.ptr) fail(c, SCS_ERR_STATE, "internal: this batch view holds no sample-space copy");
   if (!c->sgram.ptr || (c->spview < 0 && c->sgram.shift != sparse_gram_shift())) {
     sync(c);
-    dfree_t(c, c->sgram.ptr);
-    dfree_t(c, c->sgram.lidx);
-    dfree(c, c->sgram.val);
+    free_blk(c, c->sgram);
     build_sample_blocked(c);
   }
-  const scs_ctx::SpBlk& B = c->sgram;
+  const SpBlkT& B = c->sgram;
   HCK(launch_sparse_sample_gram(c->rowptr, c->colidx, c->val, B.ptr, B.lidx, B.val, B.nnz, c->sp_f32, h, c->N, c->m,
                                 B.shift, Ps, NpS, c->st));
   c->gram_kname = sparse_sample_kernel_name(c->sp_f32, B.nnz);
@@ -2844,20 +2682,21 @@ void ggn_sample_direction(scs_ctx* c, const double* xh) {
   if (sharded(c)) return ggn_sample_direction_sharded(c, xh);
   const bool sps = sparse_sample_path(c);
   if (!sps && c->At && c->loss == SCS_LOSS_CALLBACK)   // the caller's J changes every step
-    HCK(launch_transpose(c->A, c->a32, c->Npad, N, m, c->At, c->mpad, c->NpS, c->st));
+    HCK(launch_transpose(c->A, c->a32, c->Npad, N, m, c->At, c->mpad, c->ss.NpS, c->st));
   if (!sps && !c->At) {
     const double* A = dense_A(c);
-    c->NpS = round_up(N, 128);
-    c->At = dalloc<double>(c, (size_t)c->NpS * c->mpad);
-    HCK(launch_transpose(A, dense_a32(c), c->Npad, N, m, c->At, c->mpad, c->NpS, c->st));
-    c->Ps = dalloc<double>(c, (size_t)c->NpS * c->NpS);
-    c->n1pad = round_up(N + 1, 128);   // row-major, zero padding (lu.hip)
-    c->Ms = dalloc<double>(c, (size_t)c->n1pad * c->n1pad);
-    c->bS = dalloc<double>(c, c->n1pad);
-    c->uN = dalloc<double>(c, c->Npad);
-    c->hvec = dalloc<double>(c, c->mpad);
-    c->hg = dalloc<double>(c, c->mpad);
-    const int nb = (int)(c->NpS / 128);
+    SampleSys& O = c->ss;   // the view's own system scratch
+    O.NpS = round_up(N, 128);
+    c->At = dalloc<double>(c, (size_t)O.NpS * c->mpad);
+    HCK(launch_transpose(A, dense_a32(c), c->Npad, N, m, c->At, c->mpad, O.NpS, c->st));
+    O.Ps = dalloc<double>(c, (size_t)O.NpS * O.NpS);
+    O.n1pad = round_up(N + 1, 128);   // row-major, zero padding (lu.hip)
+    O.Ms = dalloc<double>(c, (size_t)O.n1pad * O.n1pad);
+    O.bS = dalloc<double>(c, O.n1pad);
+    O.uN = dalloc<double>(c, c->Npad);
+    O.hvec = dalloc<double>(c, c->mpad);
+    O.hg = dalloc<double>(c, c->mpad);
+    const int nb = (int)(O.NpS / 128);
     std::vector<int2> tl((size_t)nb * (nb + 1) / 2);
     int nt = 0;
     gram_tile_list(nb, tl.data(), &nt);
@@ -2866,10 +2705,7 @@ void ggn_sample_direction(scs_ctx* c, const double* xh) {
     c->nstiles = nt;
   }
   // the system scratch: the view's own, or (sparse branch) the set kept for this size
-  SampleSys own;
-  own.NpS = c->NpS, own.n1pad = c->n1pad;
-  own.Ps = c->Ps, own.Ms = c->Ms, own.bS = c->bS, own.uN = c->uN, own.hvec = c->hvec, own.hg = c->hg;
-  const SampleSys& S = sps ? sample_sys(c, N) : own;
+  const SampleSys& S = sps ? sample_sys(c, N) : c->ss;
   double *const Ps = S.Ps, *const Ms = S.Ms, *const bS = S.bS, *const uN = S.uN, *const hvec = S.hvec, *const hg = S.hg;
   const int64_t NpS = S.NpS, n1pad = S.n1pad;
   // s, q, r (prox-GGN-SCORE.jl:44-56) -> gN, hN, wN (a callback loss filled them: ggn_cb_load)
@@ -2956,11 +2792,7 @@ void ggn_cb_load(scs_ctx* c, const double* xh, bool sample) {
     v.nstage = v.Npad / 16;
     v.A = dalloc<double>(c, (size_t)v.Npad * c->mpad);
     v.y = dalloc<double>(c, v.Npad);
-    swap_view(c, v);
-    c->generic = false;
-    alloc_nspace(c);
-    c->generic = true;
-    swap_view(c, v);
+    alloc_nspace(c, v);
     c->cbstage = dalloc<double>(c, (size_t)v.Npad * 128);
   }
   upload_panels(c, out, 0, n, n, v.Npad, v.A, 0, c->cbstage);
@@ -3505,28 +3337,20 @@ static void reset_data(scs_ctx* c) {
     c->red_cap = 0;
     c->own_red = false;
   }
-  dfree_t(c, c->A);
-  c->a32 = 0;   // the block's type goes with it; the mode (dense_f32) persists, as the solver choice does
+  // the view in place: its buffers and fields (a32: the block's type goes with it; the mode, dense_f32,
+  // persists, as the solver choice does)
+  free_buffers(c, *c, VB_ALL);
+  static_cast<ViewData&>(*c) = ViewData();
   if (c->prod_kname == GEMV_N_F32_NAME) c->prod_kname.clear();
-  dfree_t(c, c->rowptr);
   dfree_t(c, c->colptr);
-  dfree_t(c, c->colidx);
   dfree_t(c, c->rowidx);
-  dfree(c, c->val);
   dfree(c, c->valT);
-  for (auto* B : {&c->bcsr, &c->bcsc, &c->bgram, &c->sgram}) {
-    dfree_t(c, B->ptr);
-    dfree_t(c, B->lidx);
-    dfree(c, B->val);
-    B->nblk = B->shift = 0;
-    B->nnz = 0;
-  }
+  free_blk(c, c->bgram);
   dfree_t(c, c->sgseg.seg);
   dfree_t(c, c->sgseg.T);
   dfree_t(c, c->sgseg.tptr);
   dfree_t(c, c->sgseg.sw);
   c->sgseg.state = 0;
-  c->sparse = false;
   dfree_t(c, c->Ad);
   dfree_t(c, c->ringA);
   c->sp_mode = 0;
@@ -3540,17 +3364,10 @@ static void reset_data(scs_ctx* c) {
   free_view(c, c->cbv);
   dfree_t(c, c->cbstage);
   ++c->data_gen;
-  c->nnz = 0;
-  dfree_t(c, c->y);
   dfree_t(c, c->G);
   dfree_t(c, c->Gc);
   dfree_t(c, c->tiles);
   dfree_t(c, c->utiles);
-  for (double** v : {&c->At, &c->Ps, &c->Ms, &c->bS, &c->uN, &c->hvec, &c->hg}) dfree_t(c, *v);
-  dfree_t(c, c->stiles);
-  c->n1pad = 0;
-  c->NpS = 0;
-  c->nstiles = 0;
   dfree_t(c, c->gwork);
   dfree_t(c, c->gcomb);
   dfree_t(c, c->ptiles);
@@ -3682,39 +3499,45 @@ static void join_src_stream(scs_ctx* c, hipStream_t src_stream) {
 
 // y of a device door: a host or a device pointer (the library asks the pointer's attributes)
 // (multi-output: N x K column-major with leading dimension N -> the view's stride Npad)
-static void copy_y_any(scs_ctx* c, const double* y, int64_t N) {
+static void copy_y_any(scs_ctx* c, ViewData& v, const double* y, int64_t N) {
   if (!y || N <= 0) return;
   const bool ydev = is_device_ptr(y, nullptr);
   const hipMemcpyKind kind = ydev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   if (multi(c))
-    HCK(hipMemcpy2DAsync(c->y, sizeof(double) * c->Npad, y, sizeof(double) * N, sizeof(double) * N, c->nout, kind,
+    HCK(hipMemcpy2DAsync(v.y, sizeof(double) * v.Npad, y, sizeof(double) * N, sizeof(double) * N, c->nout, kind,
                          c->st));
   else
-    HCK(hipMemcpyAsync(c->y, y, sizeof(double) * N, kind, c->st));
+    HCK(hipMemcpyAsync(v.y, y, sizeof(double) * N, kind, c->st));
 }
 
-// N rows of src -> the context's (current view's) A and y.  Host rows: panel by panel through the
-// column-major staging buffer.  Device rows: one re-tile pass that writes the whole block, padding
-// included.  Ends with the stream drained: the caller may free the source.
-static void load_dense(scs_ctx* c, const DenseSrc& s, int64_t N, const double* y) {
+// y of a host door (multi-output: N x nout, column-major)
+static void upload_y(scs_ctx* c, ViewData& v, const double* y, int64_t N) {
+  if (!y || N <= 0) return;
+  if (multi(c)) {
+    copy_y_any(c, v, y, N);
+    sync(c);   // a pageable host source: the call returns with the copy done
+  } else {
+    h2d(c, v.y, y, N);
+  }
+}
+
+// N rows of src -> the A and y of v (the data in place, or a view being built).  Host rows: panel by
+// panel through the column-major staging buffer.  Device rows: one re-tile pass that writes the whole
+// block, padding included.  Ends with the stream drained: the caller may free the source.
+static void load_dense(scs_ctx* c, ViewData& v, const DenseSrc& s, int64_t N, const double* y) {
   if (s.dev) {
     join_src_stream(c, s.src_stream);
-    HCK(launch_tile_device(s.A, s.in32, s.sn, s.sm, N, c->dc, c->Npad, c->dcp, c->A, c->a32, c->st));
-    copy_y_any(c, y, N);
+    HCK(launch_tile_device(s.A, s.in32, s.sn, s.sm, N, c->dc, v.Npad, c->dcp, v.A, v.a32, c->st));
+    copy_y_any(c, v, y, N);
     sync(c);
     return;
   }
   if (N <= 0) return;
-  double* C = dalloc<double>(c, (size_t)c->Npad * (s.in32 ? 64 : 128));   // Npad x 128 elements
-  upload_panels(c, s.A, s.in32, N, s.lda, c->Npad, c->A, c->a32, C);
+  double* C = dalloc<double>(c, (size_t)v.Npad * (s.in32 ? 64 : 128));   // Npad x 128 elements
+  upload_panels(c, s.A, s.in32, N, s.lda, v.Npad, v.A, v.a32, C);
   sync(c);
   dfree_t(c, C);
-  if (y && multi(c)) {
-    copy_y_any(c, y, N);
-    sync(c);   // a pageable host source: the call returns with the copy done
-  } else if (y) {
-    h2d(c, c->y, y, N);
-  }
+  upload_y(c, v, y, N);
 }
 
 // scs_set_data (in32 = 0) / scs_set_data_f32 (in32 = 1: host floats, stored as they are) /
@@ -3747,7 +3570,7 @@ static int set_data_any(scs_ctx* c, int64_t N, int64_t m, const DenseSrc& src, c
       c->a32 = c->dense_f32;
       c->A = alloc_A(c, c->Npad, c->a32, !src.dev);
       c->y = dalloc<double>(c, c->Npad * kout(c));
-      load_dense(c, src, N, y);
+      load_dense(c, *c, src, N, y);
     }
     alloc_mspace(c);
     alloc_nspace(c);
@@ -3822,8 +3645,8 @@ int scs_set_sparse_sample(scs_ctx* c, int on) {
     free_sparse_views(c);
     free_sample_sys(c);
     if (c->sparse) {
-      for (double** p : {&c->At, &c->Ps, &c->Ms, &c->bS, &c->uN, &c->hvec, &c->hg, &c->Ad}) dfree_t(c, *p);
-      dfree_t(c, c->stiles);
+      free_buffers(c, *c, VB_SAMPLE);
+      dfree_t(c, c->Ad);
       c->nstiles = 0;
     }
     invalidate_caches(c);
@@ -3978,18 +3801,18 @@ static void upload_vals(scs_ctx* c, void* dst, const double* src, int64_t n, int
 // Sort each row's entries by index (in place: the arrays are replaced by sorted
 // copies) and build the LDS-blocked copy B (sparse.hip).
 // kcols > 1: the K-column layout of multi_sparse.hip (finer blocks, the same slots and padding).
-static void build_blocked(scs_ctx* c, int64_t nrows, int64_t ncols, int64_t* ptr, int*& idx, void*& val,
-                          scs_ctx::SpBlk& B, int kcols = 1) {
-  const int64_t nnz = c->nnz;
+// The arrays hold nnz entries of the float (f32) or double type.
+static void build_blocked(scs_ctx* c, int64_t nnz, int f32, int64_t nrows, int64_t ncols, int64_t* ptr, int*& idx,
+                          void*& val, SpBlkT& B, int kcols = 1) {
   size_t tb = 0;
   if (nnz > 0 && nrows > 0) {
     int end_bit = 1;
     while ((int64_t(1) << end_bit) < ncols) ++end_bit;
     int* idx_s = dalloc<int>(c, nnz);
-    void* val_s = dalloc_vals(c, nnz, c->sp_f32);
-    HCK(sort_segments(nullptr, &tb, idx, idx_s, val, val_s, c->sp_f32, nnz, nrows, ptr, end_bit, c->st));
+    void* val_s = dalloc_vals(c, nnz, f32);
+    HCK(sort_segments(nullptr, &tb, idx, idx_s, val, val_s, f32, nnz, nrows, ptr, end_bit, c->st));
     void* tmp = dalloc<char>(c, tb);
-    HCK(sort_segments(tmp, &tb, idx, idx_s, val, val_s, c->sp_f32, nnz, nrows, ptr, end_bit, c->st));
+    HCK(sort_segments(tmp, &tb, idx, idx_s, val, val_s, f32, nnz, nrows, ptr, end_bit, c->st));
     sync(c);
     dfree(c, tmp);
     dfree_t(c, idx);
@@ -4008,7 +3831,7 @@ static void build_blocked(scs_ctx* c, int64_t nrows, int64_t ncols, int64_t* ptr
     HCK(blk_count(ptr, idx, nrows, B.shift, cnt, first, c->st));
     // segments in whole slots of 4 (fp64) / 8 (fp32) entries (padding: index 16384 = the SpMV's
     // zero slot, value 0; launch_spmv_blk)
-    HCK(blk_pad(cnt, nk, c->sp_f32, c->st));
+    HCK(blk_pad(cnt, nk, f32, c->st));
     tb = 0;
     HCK(blk_scan(nullptr, &tb, cnt, B.ptr, nk + 1, c->st));
     void* tmp = dalloc<char>(c, tb);
@@ -4019,12 +3842,12 @@ static void build_blocked(scs_ctx* c, int64_t nrows, int64_t ncols, int64_t* ptr
     dfree(c, tmp);
     B.lidx = dalloc<uint16_t>(c, nnzp + 8);
     HCK(hipMemsetD16Async((hipDeviceptr_t)B.lidx, (unsigned short)spmv_pad_index(), (size_t)(nnzp + 8), c->st));
-    B.val = dalloc_vals(c, nnzp + 8, c->sp_f32);
-    HCK(blk_scatter(ptr, idx, val, c->sp_f32, nrows, B.shift, B.ptr, first, B.lidx, B.val, c->st));
+    B.val = dalloc_vals(c, nnzp + 8, f32);
+    HCK(blk_scatter(ptr, idx, val, f32, nrows, B.shift, B.ptr, first, B.lidx, B.val, c->st));
     sync(c);
   } else {
     B.lidx = dalloc<uint16_t>(c, 4);
-    B.val = dalloc_vals(c, 4, c->sp_f32);
+    B.val = dalloc_vals(c, 4, f32);
   }
   sync(c);
   dfree_t(c, cnt);
@@ -4059,20 +3882,22 @@ static void transpose_csr(scs_ctx* c) {
 static void finish_sparse(scs_ctx* c, bool transpose) {
   c->ms_kernel = multi(c) ? multi_sparse_arm(c->nout, c->sp_f32) : 0;   // read once, here: one set of copies per context
   const int kc = c->ms_kernel ? c->nout : 1;
-  build_blocked(c, c->N, c->dc, c->rowptr, c->colidx, c->val, c->bcsr, kc);
+  build_blocked(c, c->nnz, c->sp_f32, c->N, c->dc, c->rowptr, c->colidx, c->val, c->bcsr, kc);
   if (transpose) transpose_csr(c);
-  build_blocked(c, c->dc, c->N, c->colptr, c->rowidx, c->valT, c->bcsc, kc);
+  build_blocked(c, c->nnz, c->sp_f32, c->dc, c->N, c->colptr, c->rowidx, c->valT, c->bcsc, kc);
   alloc_mspace(c);
   alloc_nspace(c);
   sync(c);
   c->has_data = true;
 }
 
-// the held-out counterpart: CSR only (the arm of a sparse A's context is the one its data door read)
-static void finish_sparse_test(scs_ctx* c, int64_t N, bool data_sparse) {
-  const int arm = !multi(c) ? 0 : data_sparse ? c->ms_kernel : multi_sparse_arm(c->nout, c->sp_f32);
-  build_blocked(c, N, c->dc, c->rowptr, c->colidx, c->val, c->bcsr, arm ? c->nout : 1);
-  alloc_nspace(c);
+// the held-out counterpart, on the held-out view with its CSR and y in place: the row copy only (the arm
+// of a sparse A's context is the one its data door read), the workspace sized by the data's column copy
+static void finish_sparse_test(scs_ctx* c) {
+  NView& v = c->tset.v;
+  const int arm = !multi(c) ? 0 : c->sparse ? c->ms_kernel : multi_sparse_arm(c->nout, v.sp_f32);
+  build_blocked(c, v.nnz, v.sp_f32, v.N, c->dc, v.rowptr, v.colidx, v.val, v.bcsr, arm ? c->nout : 1);
+  alloc_nspace(c, v, c->bcsc);
   sync(c);
   c->tset.on = true;
 }
@@ -4116,12 +3941,7 @@ int scs_set_sparse(scs_ctx* c, int64_t N, int64_t m, int64_t nnz, const int64_t*
       upload_vals(c, c->valT, valT, nnz, c->sp_f32);
     }
     c->y = dalloc<double>(c, c->Npad * kout(c));
-    if (y && N > 0 && multi(c)) {   // N x nout, column-major
-      copy_y_any(c, y, N);
-      sync(c);   // a pageable host source: the call returns with the copy done
-    } else if (y && N > 0) {
-      h2d(c, c->y, y, N);
-    }
+    upload_y(c, *c, y, N);
     finish_sparse(c, false);
   });
 }
@@ -4245,7 +4065,7 @@ int scs_set_sparse_device(scs_ctx* c, int64_t N, int64_t m, int64_t nnz, const v
     c->colidx = b.colidx;
     c->val = b.val;
     c->y = dalloc<double>(c, c->Npad * kout(c));
-    copy_y_any(c, y, N);
+    copy_y_any(c, *c, y, N);
     finish_sparse(c, true);
   });
 }
@@ -4284,8 +4104,8 @@ int scs_gen_sparse(scs_ctx* c, const scs_synth* s, int f32) {
     HCK(hipMemcpyAsync(dmaps, maps.data(), maps.size(), hipMemcpyHostToDevice, c->st));
     HCK(launch_gen_sparse(N, m, k, s->seed, dmaps, c->sp_f32, 1.0 / std::sqrt((double)k), c->rowptr, c->colidx,
                           c->val, c->colptr, c->rowidx, c->valT, c->st));
-    build_blocked(c, N, m, c->rowptr, c->colidx, c->val, c->bcsr);
-    build_blocked(c, m, N, c->colptr, c->rowidx, c->valT, c->bcsc);
+    build_blocked(c, nnz, c->sp_f32, N, m, c->rowptr, c->colidx, c->val, c->bcsr);
+    build_blocked(c, nnz, c->sp_f32, m, N, c->colptr, c->rowidx, c->valT, c->bcsc);
     alloc_nspace(c);
     HCK(launch_gen_uniform(c->xn, m, s->seed, -1.5, 1.5, c->st));
     const int ns = matvec_n(c, c->xn, c->nsplit);
@@ -4379,9 +4199,8 @@ static int set_test_any(scs_ctx* c, int64_t N, const DenseSrc& src, const double
     if (lda < N) fail(c, SCS_ERR_ARG, "test data: lda (%lld) < N (%lld)", (long long)lda, (long long)N);
     (void)row0;
     test_view_dims(c, N, Nglob, false, !src.dev);
-    TestScope ts(c);
-    load_dense(c, src, N, y);
-    alloc_nspace(c);
+    load_dense(c, c->tset.v, src, N, y);
+    alloc_nspace(c, c->tset.v);
     sync(c);
     c->tset.on = true;
   });
@@ -4426,25 +4245,19 @@ int scs_set_test_sparse(scs_ctx* c, int64_t N, int64_t nnz, const int64_t* rowpt
     if (nnz > INT32_MAX * 64LL) fail(c, SCS_ERR_ARG, "sparse test data: nnz too large");
     (void)row0;
     test_view_dims(c, N, Nglob, true);
-    const bool data_sparse = c->sparse;
-    TestScope ts(c);
-    c->sp_f32 = f32 ? 1 : 0;
-    c->nnz = nnz;
-    c->rowptr = dalloc<int64_t>(c, N + 1);
-    c->colidx = dalloc<int>(c, nnz);
-    c->val = dalloc_vals(c, nnz, c->sp_f32);
-    HCK(hipMemcpyAsync(c->rowptr, rowptr, sizeof(int64_t) * (N + 1), hipMemcpyHostToDevice, c->st));
+    NView& v = c->tset.v;
+    v.sp_f32 = f32 ? 1 : 0;
+    v.nnz = nnz;
+    v.rowptr = dalloc<int64_t>(c, N + 1);
+    v.colidx = dalloc<int>(c, nnz);
+    v.val = dalloc_vals(c, nnz, v.sp_f32);
+    HCK(hipMemcpyAsync(v.rowptr, rowptr, sizeof(int64_t) * (N + 1), hipMemcpyHostToDevice, c->st));
     if (nnz > 0) {
-      HCK(hipMemcpyAsync(c->colidx, colidx, sizeof(int) * nnz, hipMemcpyHostToDevice, c->st));
-      upload_vals(c, c->val, val, nnz, c->sp_f32);
+      HCK(hipMemcpyAsync(v.colidx, colidx, sizeof(int) * nnz, hipMemcpyHostToDevice, c->st));
+      upload_vals(c, v.val, val, nnz, v.sp_f32);
     }
-    if (N > 0 && multi(c)) {   // N x nout, column-major
-      copy_y_any(c, y, N);
-      sync(c);
-    } else if (N > 0) {
-      h2d(c, c->y, y, N);
-    }
-    finish_sparse_test(c, N, data_sparse);
+    upload_y(c, v, y, N);
+    finish_sparse_test(c);
   });
 }
 
@@ -4466,15 +4279,14 @@ int scs_set_test_sparse_device(scs_ctx* c, int64_t N, int64_t nnz, const void* d
     free_test(c);
     (void)row0;
     test_view_dims(c, N, Nglob, true);
-    const bool data_sparse = c->sparse;
-    TestScope ts(c);
-    c->sp_f32 = f32 ? 1 : 0;
-    c->nnz = nnz;
-    c->rowptr = b.rowptr;
-    c->colidx = b.colidx;
-    c->val = b.val;
-    copy_y_any(c, y, N);
-    finish_sparse_test(c, N, data_sparse);
+    NView& v = c->tset.v;
+    v.sp_f32 = f32 ? 1 : 0;
+    v.nnz = nnz;
+    v.rowptr = b.rowptr;
+    v.colidx = b.colidx;
+    v.val = b.val;
+    copy_y_any(c, v, y, N);
+    finish_sparse_test(c);
   });
 }
 
@@ -4490,15 +4302,15 @@ int scs_gen_test_data(scs_ctx* c, const scs_synth* s) {
     refuse_f32_quadratic(c, c->dense_f32);
     free_test(c);
     test_view_dims(c, s->N, s->N_global, false);
-    TestScope ts(c);
-    alloc_nspace(c);
+    NView& v = c->tset.v;
+    alloc_nspace(c, v);
     const double scale = (s->kind == 3) ? 1.0 : 1.0 / std::sqrt((double)s->m);
     // rows [row0, row0 + N) of the same generator as scs_gen_data: with row0 >= the data's N_global
     // they are held-out samples of the same distribution (the same x_true)
-    HCK(launch_gen_A(c->A, c->a32, c->Npad, c->N, c->m, c->mpad, s->row0, s->seed, scale, c->st));
+    HCK(launch_gen_A(v.A, v.a32, v.Npad, v.N, c->m, c->mpad, s->row0, s->seed, scale, c->st));
     HCK(launch_gen_xtrue(c->xn, c->m, s->seed, s->density, c->st));
-    HCK(launch_gemv_n(c->A, c->a32, c->nstage, c->Npad, c->mpad, c->xn, 1, c->zpart, c->Npad, c->st));
-    HCK(launch_gen_y(s->kind, c->zpart, c->y, c->N, s->row0, s->seed, c->st));
+    HCK(launch_gemv_n(v.A, v.a32, v.nstage, v.Npad, c->mpad, c->xn, 1, v.zpart, v.Npad, c->st));
+    HCK(launch_gen_y(s->kind, v.zpart, v.y, v.N, s->row0, s->seed, c->st));
     sync(c);
     c->tset.on = true;
   });

@@ -430,6 +430,7 @@ class Context:
             if rc != SCS_OK:
                 raise ScsError(rc, f"scs_create(device={device}) failed")
         self.h = h
+        self._pid = os.getpid()
         self.device = device
         self.devices = list(devices) if devices is not None else [device]
         self._keep = []  # ctypes callbacks / buffers that must outlive the context
@@ -447,7 +448,10 @@ class Context:
 
     def close(self):
         if getattr(self, "h", None):
-            lib.scs_destroy(self.h)
+            # a forked child (multiprocessing's fork start method, a Manager's server) inherits the object
+            # but neither the HIP runtime's state nor a group's worker threads: the handle is the parent's
+            if getattr(self, "_pid", None) == os.getpid():
+                lib.scs_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -341,3 +341,89 @@ def test_two_ranks_one_batch_on_rank_0_alone(tmp_path):
     assert r0["obj"] == r1["obj"] and np.array_equal(bits(r0["x"]), bits(r1["x"]))   # identical bits on both ranks
     np.testing.assert_allclose(r0["obj"], full["obj"], rtol=1e-10)
     np.testing.assert_allclose(r0["x"], full["x"], rtol=1e-8, atol=1e-12)
+
+
+# ---- 7. the data in place comes back -------------------------------------------------------------------
+# batch_info() after the two ProxLQNSCORE views, after the two sample-space views, at the end
+VIEW_INFO = ((2, 26272, 2), (2, 29360, 2), (1, 8080, 3))
+
+
+def test_data_in_place_restored_after_every_kind_of_view():
+    """One context, every kind of view built and used on it in turn (a dense batch view, a sparse one,
+    its sample-space form, a sparse held-out set, a step that fails with a batch view in place): after
+    each, f(x0), ∇f(x0), the CSR and y read back and the dense block's data_info are, bit for bit,
+    what they were before any view existed.  (data_info()[2], the bytes the context holds, grows with
+    the views kept and is not part of the comparison.)
+
+    N = 300, m = 40, 6 entries per row, row 7 empty, 17 held-out rows; batches of 64, 64, 64, 64 and 44
+    rows.  With m = 40 none of those takes ProxGGNSCORE's sample-space branch (n_b + 1 <= m), so that
+    step runs on a second list with batches of 30 and 39 = m - 1 rows.  The views' count, bytes and
+    builds are the figures the commit before the view's one definition gives for this sequence."""
+    N, m = 300, 40
+    rng = np.random.default_rng(41)
+    A = (sp.random(N, m, density=6.0 / m, random_state=9, format="csr") * 2.0).tolil()
+    A[7, :] = 0.0
+    A = A.tocsr()
+    A.eliminate_zeros()
+    assert A[7].nnz == 0 and 5.0 < A.nnz / N < 7.0
+    y = (rng.random(N) < 0.5).astype(float)
+    x0 = rng.standard_normal(m) * 0.3
+    At = sp.random(17, m, density=6.0 / m, random_state=10, format="csr") * 2.0
+    yt = (rng.random(17) < 0.5).astype(float)
+    perm = rng.permutation(N)
+    batches = [perm[i:i + 64] for i in range(0, N, 64)]
+    assert [b.size for b in batches] == [64, 64, 64, 64, 44]
+    small = [perm[:30], perm[100:139]]
+    p = scsopt.Problem(A, y, x0, losses.logistic_ce(1.0 / N), LAM, out_fn=losses.sigmoid_ce(1.0 / N), Atest=At, ytest=yt)
+    p.configure("l1", hmu())
+
+    def state():
+        S, ys = p.get_sparse()
+        return (bits(p.fx(x0)), bits(p.gradx(x0)), S.indptr.copy(), S.indices.copy(), bits(S.data), bits(ys),
+                np.array(p.data_info()[:2]), np.array([p.N, p.nnz]))
+    before = state()
+    assert np.isfinite(p.fx(x0)) and np.all(np.isfinite(p.gradx(x0)))
+
+    def unchanged(what):
+        for i, (a, b) in enumerate(zip(before, state())):
+            assert np.array_equal(a, b), (what, i)
+
+    def one_step(meth, batch):
+        init_method(meth, p)
+        xn, pri = step(meth, p, "l1", hmu(), x0, x0, 1, batch=batch)
+        assert np.all(np.isfinite(xn)) and np.isfinite(pri), (type(meth).__name__, batch)
+    try:
+        p.set_batches(batches)
+        one_step(lqn(), 0)
+        unchanged("dense batch view")
+        assert p.batch_info() == (0, 0, 0)
+        p.set_sparse_batches(True)
+        one_step(lqn(), 1)
+        unchanged("sparse batch view")
+        one_step(lqn(), 4)
+        unchanged("sparse batch view, 44 rows")
+        info_lqn = p.batch_info()
+        p.set_sparse_sample(True)
+        p.set_batches(small)
+        for b in (0, 1):
+            one_step(scsopt.ProxGGNSCORE(), b)
+            unchanged("sample-space view %d" % b)
+        info_ggn = p.batch_info()
+        ft = p.ftest(x0)
+        unchanged("held-out set")
+        assert np.isfinite(ft) and ft == p.ftest(x0)
+        p.select_batch(1)
+        p.select_batch(-1)
+        unchanged("select_batch(-1)")
+        init_method(scsopt.ProxGGNSCORE(ss_type=4), p)   # refused at the step size, with the view in place
+        with pytest.raises(scsopt.ScsReferenceError, match="ss_type"):
+            step(scsopt.ProxGGNSCORE(ss_type=4), p, "l1", hmu(), x0, x0, 1, batch=0)
+        p.select_batch(-1)
+        unchanged("a step that failed on a batch view")
+        one_step(lqn(), 0)      # the context is still usable, and the data still comes back
+        unchanged("the step after the failure")
+        print("batch_info", info_lqn, info_ggn, p.batch_info())
+        assert (info_lqn, info_ggn, p.batch_info()) == VIEW_INFO
+    finally:
+        p.set_batches(None)
+        p.ctx.close()
