@@ -263,8 +263,9 @@ int scs_set_loss_samplewise(scs_ctx* ctx, scs_samplewise_fn* fn, void* user, int
  * sparse A (scs_set_sparse*, scs_set_test_sparse*) unless scs_set_sparse_outputs is on (below),
  * scs_gen_sparse, scs_gen_data, scs_set_compute_f32, nranks > 1 and multi-device contexts,
  * scs_set_batches, any other loss kind, and ProxGGNSCORE when N*nout + 1 <= d*nout (the reference
- * then takes its sample-space branch, whose step differs: use the callback loss for it).  The mode
- * persists across data doors, as scs_set_dense_f32 does.                                        */
+ * then takes its sample-space branch, whose step differs: scs_set_multi_sample below runs it on a
+ * dense A; without it use the callback loss).  The mode persists across data doors, as
+ * scs_set_dense_f32 does.                                                                        */
 /* (With nout set scs_get_dims reports A's column count d as m, scs_get_data returns y as nr x nout
  * with leading dimension nr, and the single-vector kernel-level doors -- scs_gemv_n_eval,
  * scs_gemv_t_eval, scs_gram_eval, scs_solve_eval, scs_gram_atv_eval, scs_sample_gram_eval -- are
@@ -286,6 +287,21 @@ int scs_get_outputs(scs_ctx* ctx, int* nout, int64_t* nvar);
  * sample-space shape and the single-vector kernel doors; scs_set_sparse_sample is stored without
  * effect.                                                                                          */
 int scs_set_sparse_outputs(scs_ctx* ctx, int on);
+/* ProxGGNSCORE's sample-space branch of a multi-output loss (opt-in; off by default).  With the
+ * switch on, nout = K set and N*K + 1 <= d*K, a ProxGGNSCORE step solves the reference's
+ * sample-space system (prox-GGN-SCORE.jl:124-127, J = I_K (x) A) of order n1 = N*K + 1 on the device
+ * instead of being refused.  Rows and columns (i, k) = i + N*k, last index n = N*K; h = 1 ./ Hr,
+ * P_l = A diag(h_l) Aᵀ, u_l = A (h_l .* lambda gr_l), Q_i the K x K block of hess_fy:
+ *   M[(i,k),(j,l)] = δ_ij δ_kl + Q_i[k,l] P_l[i,j],  M[(i,k),n] = sum_l Q_i[k,l] u_l[i],  M[n,:] = e_n,
+ *   b = [vec(R); 1],  d_l = -h_l .* (Aᵀ B_l + lambda gr_l B[n]).
+ * K Grams of the single-output sample-space launch (one N x N buffer), one assembly launch per
+ * column block, the LU (the QR in SCS_SOLVER_REFERENCE mode) of the order-n1 system.  Memory: the
+ * transposed copy of A (N x d doubles), N² and n1² doubles.  With N*K + 1 > d*K the feature branch
+ * runs as with the switch off; ProxNSCORE / ProxLQNSCORE are unaffected; stored without effect
+ * while nout is unset.  Still refused (SCS_ERR_ARG) in the sample-space shape with the switch on: a
+ * sparse A (scs_set_sparse_outputs included) -- the branch needs a dense A.  Refused on multi-device
+ * contexts as scs_set_outputs is.                                                                  */
+int scs_set_multi_sample(scs_ctx* ctx, int on);
 
 /* ---- data  (Problem(A, y, ...) -- problems.jl:61-81) --------------------- */
 /* Upload host A (column-major, N x m, leading dim lda) and y (N).  N is the
@@ -672,6 +688,14 @@ int scs_multi_products_eval(scs_ctx* ctx, int K, const double* X, const double* 
  * column-major, ldg >= nvar, both triangles) before λ diag Hr, g = vec(Aᵀ R) and *f = f(x).  Any
  * output may be NULL.                                                                              */
 int scs_multi_system_eval(scs_ctx* ctx, const double* x, double* G, int64_t ldg, double* g, double* f);
+/* The sample-space system of a multi-output ProxGGNSCORE step at x (scs_set_multi_sample), by the
+ * step's own forward pass and assembly, before the solve: M of order n1 = N*nout + 1 (column-major,
+ * ldm >= n1; nothing is written beyond order n1) and b (n1).  The regularizer and the smoother must
+ * be set (h = 1 ./ Hr and lambda gr enter the system).  M or b may be NULL.  SCS_ERR_STATE without
+ * nout or without the switch; SCS_ERR_ARG when N*nout + 1 > d*nout (the feature branch's shape) or
+ * on a sparse A.  With timing on, the assembly launches (one per column block, and the tail) are
+ * bracketed by events of their own and reported as step_ms / step_calls: no step runs in here.     */
+int scs_multi_sample_system_eval(scs_ctx* ctx, const double* x, double* M, int64_t ldm, double* b);
 
 /* ---- timing ------------------------------------------------------------- */
 /* on = 0: off; 1: HIP events around every Gram / product / solve / step; n > 1: in

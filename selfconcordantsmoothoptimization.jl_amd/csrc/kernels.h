@@ -441,6 +441,23 @@ hipError_t launch_multi_weight(int loss, const double* P, const double* s, int k
 // the d x d Gram Gd (upper triangle valid, leading dimension ldd) -> blocks (k, l) and (l, k) of G
 hipError_t launch_multi_place(const double* Gd, int64_t ldd, int64_t d, int k, int l, double* G, int64_t ldg,
                               hipStream_t st);
+// ProxGGNSCORE's sample-space branch of a multi-output loss (scs_set_multi_sample): rows / columns
+// (i, k) = i + N·k of the row-major system Ms (row stride ldm = round_up(N·K + 1, 128), zero padding).
+// prep: hP[l*dpad + j] = 1 / Hr[j + d*l] (0 beyond d), hg[j + d*l] = h (λ gr).  assemble: column block l,
+// M[(i,k),(j,l)] = δ + Q_i[k,l] P_l[i,j] for all k, from the symmetrized P_l (Ps, ldp), P in `P`, s in `s`.
+// tail: the last column Σ_l Q_i[k,l] u_l[i], the last row e_n, the padding and b = [vec(R); 1; 0...].
+// spread: V (N x K, stride Npad, zero rows beyond N) <- B[0 : N·K].  direction: d = -(h∘t + hg·B[n]).
+hipError_t launch_multi_sample_prep(const double* Hr, const double* gr, double lam, int64_t d, int64_t dpad, int K,
+                                    double* hP, double* hg, hipStream_t st);
+hipError_t launch_multi_sample_assemble(int loss, int K, int l, const double* Ps, int64_t ldp, const double* P,
+                                        const double* s, int64_t N, int64_t Npad, double c, double* Ms, int64_t ldm,
+                                        hipStream_t st);
+hipError_t launch_multi_sample_tail(int loss, int K, const double* P, const double* s, const double* u,
+                                    const double* R, int64_t N, int64_t Npad, double c, double* Ms, int64_t ldm,
+                                    double* b, hipStream_t st);
+hipError_t launch_multi_sample_spread(const double* B, int64_t N, int64_t Npad, int K, double* V, hipStream_t st);
+hipError_t launch_multi_sample_direction(const double* hP, const double* t, const double* hg, const double* B,
+                                         int64_t n, int64_t d, int64_t dpad, int K, double* dir, hipStream_t st);
 
 // ---- multi_sparse.hip: the same two products on a sparse A (scs_set_sparse_outputs), one pass over the
 // nonzeros for all K columns.  The blocked copy is build_blocked's at shift multi_spmm_shift(ncols, K)

@@ -316,20 +316,24 @@ hipError_t launch_multi_epilogue(int loss, int flags, int K, const double* zpart
   return hipGetLastError();
 }
 
-// w_kl,i = Q_i[k, l]: softmax c s_i (δ_kl P_ik - P_ik P_il); multi LS c (k = l only).  Rows N..Npad: 0.
+// Q_i[k, l]: softmax c s_i (δ_kl P_ik - P_ik P_il); multi LS c δ_kl.  The one definition: the feature
+// branch's weight vectors and the sample-space assembly form the same bits.
+__device__ __forceinline__ double multi_q_entry(int loss, const double* __restrict__ P, const double* __restrict__ sv,
+                                                int k, int l, int64_t n, int64_t Npad, double c) {
+  if (loss == SCS_LOSS_SOFTMAX_CE) {
+    const double pk = P[(int64_t)k * Npad + n], pl = P[(int64_t)l * Npad + n];
+    return (k == l) ? c * sv[n] * (pk - pk * pl) : c * sv[n] * (-(pk * pl));
+  }
+  return (k == l) ? c : 0.0;
+}
+
+// w_kl,i = Q_i[k, l] (multi LS: called with k = l only).  Rows N..Npad: 0.
 __global__ void multi_weight_kernel(int loss, const double* __restrict__ P, const double* __restrict__ sv, int k,
                                     int l, int64_t N, int64_t Npad, double c, double* __restrict__ w) {
   const int64_t n = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (n >= Npad) return;
   double v = 0.0;
-  if (n < N) {
-    if (loss == SCS_LOSS_SOFTMAX_CE) {
-      const double pk = P[(int64_t)k * Npad + n], pl = P[(int64_t)l * Npad + n];
-      v = (k == l) ? c * sv[n] * (pk - pk * pl) : c * sv[n] * (-(pk * pl));
-    } else {
-      v = c;
-    }
-  }
+  if (n < N) v = (loss == SCS_LOSS_SOFTMAX_CE) ? multi_q_entry(loss, P, sv, k, l, n, Npad, c) : c;
   w[n] = v;
 }
 
@@ -356,6 +360,170 @@ hipError_t launch_multi_place(const double* Gd, int64_t ldd, int64_t d, int k, i
                               hipStream_t st) {
   hipLaunchKernelGGL(multi_place_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(d, 256), 8), (unsigned)d), dim3(256),
                      0, st, Gd, ldd, d, k, l, G, ldg);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// ProxGGNSCORE's sample-space branch of a multi-output loss (scs_set_multi_sample, N·K + 1 <= d·K;
+// prox-GGN-SCORE.jl:124-127 with J = I_K ⊗ A).  Rows and columns (i, k) = i + N·k, last index n = N·K:
+//   M[(i,k),(j,l)] = δ_ij δ_kl + Q_i[k,l] P_l[i,j],   P_l = A diag(h_l) Aᵀ,  h = 1 ./ Hr
+//   M[(i,k), n]    = Σ_l Q_i[k,l] u_l[i],              u_l = A (h_l ∘ λ gr_l)
+//   M[n, ·] = e_n,  b = [vec(R); 1],  d_l = -(h_l ∘ Aᵀ B_l + (h_l ∘ λ gr_l) B[n])
+// M is row-major with row stride ldm = round_up(n + 1, 128) and zero padding (lu.hip).
+// ---------------------------------------------------------------------------
+// hP[l*dpad + j] = 1 / Hr[j + d*l] (0 for d <= j < dpad: the Gram's weights of block l, padded as the
+// single-output hvec is); hg[j + d*l] = h (λ gr) (vec layout: the operand of A X̃ and of the direction)
+__global__ void multi_sample_prep_kernel(const double* __restrict__ Hr, const double* __restrict__ gr, double lam,
+                                         int64_t d, int64_t dpad, int K, double* __restrict__ hP,
+                                         double* __restrict__ hg) {
+  const int64_t o = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (o >= dpad * K) return;
+  const int64_t l = o / dpad, j = o - l * dpad;
+  double h = 0.0;
+  if (j < d) {
+    const int64_t f = j + d * l;
+    h = 1.0 / Hr[f];   // Hdiag_inv = 1 ./ Hr_diag (prox-GGN-SCORE.jl:64)
+    hg[f] = h * (lam * gr[f]);
+  }
+  hP[o] = h;
+}
+
+hipError_t launch_multi_sample_prep(const double* Hr, const double* gr, double lam, int64_t d, int64_t dpad, int K,
+                                    double* hP, double* hg, hipStream_t st) {
+  hipLaunchKernelGGL(multi_sample_prep_kernel, dim3((unsigned)ceil_div(dpad * K, 256)), dim3(256), 0, st, Hr, gr, lam,
+                     d, dpad, K, hP, hg);
+  return hipGetLastError();
+}
+
+// Column block l of M from P_l (Ps: symmetric, both triangles, leading dimension ldp): one workgroup
+// takes MSA_ROWS rows i of P_l and 512 of its columns, reads each element once and writes it into the K
+// blocks (k, l).  The K weights Q_i[k,l] of a row are formed once per workgroup (LDS).  Entry = δ + w·p:
+// one product, one add (no contraction).  A thread owns two adjacent columns chosen so that the pair
+// is 16-byte aligned in M (ldm is even, so the parity of N·l + j decides it for every row); the pairs
+// at the two ends of a row of odd offset are single stores.
+constexpr int MSA_ROWS = 8;
+
+__global__ __launch_bounds__(256) void multi_sample_assemble_kernel(int loss, int K, int l,
+                                                                    const double* __restrict__ Ps, int64_t ldp,
+                                                                    const double* __restrict__ P,
+                                                                    const double* __restrict__ sv, int64_t N,
+                                                                    int64_t Npad, double c, double* __restrict__ Ms,
+                                                                    int64_t ldm) {
+  __shared__ double w[MSA_ROWS][16];
+  const int tid = threadIdx.x;
+  const int64_t i0 = (int64_t)blockIdx.y * MSA_ROWS;
+  if (tid < MSA_ROWS * 16) {
+    const int r = tid >> 4, k = tid & 15;
+    const int64_t i = i0 + r;
+    w[r][k] = (i < N && k < K) ? multi_q_entry(loss, P, sv, k, l, i, Npad, c) : 0.0;
+  }
+  __syncthreads();
+  const int64_t cb = N * l;   // first column of block l
+  const int64_t j0 = ((int64_t)blockIdx.x * 256 + tid) * 2 - (cb & 1);
+  const bool v0 = j0 >= 0 && j0 < N, v1 = j0 + 1 < N;
+  if (!v0 && !v1) return;
+  double p0[MSA_ROWS], p1[MSA_ROWS];
+#pragma unroll
+  for (int r = 0; r < MSA_ROWS; ++r) {
+    const int64_t i = i0 + r;
+    const double* pr = Ps + i * ldp;
+    p0[r] = (i < N && v0) ? pr[j0] : 0.0;
+    p1[r] = (i < N && v1) ? pr[j0 + 1] : 0.0;
+  }
+#pragma unroll
+  for (int r = 0; r < MSA_ROWS; ++r) {
+    const int64_t i = i0 + r;
+    if (i >= N) break;
+    for (int k = 0; k < K; ++k) {
+      const double wk = w[r][k];
+      const double e0 = __dadd_rn((k == l && i == j0) ? 1.0 : 0.0, __dmul_rn(wk, p0[r]));
+      const double e1 = __dadd_rn((k == l && i == j0 + 1) ? 1.0 : 0.0, __dmul_rn(wk, p1[r]));
+      double* o = Ms + (i + N * k) * ldm + cb + j0;
+      if (v0 && v1)
+        *(v2d*)o = (v2d){e0, e1};
+      else if (v0)
+        o[0] = e0;
+      else
+        o[1] = e1;
+    }
+  }
+}
+
+hipError_t launch_multi_sample_assemble(int loss, int K, int l, const double* Ps, int64_t ldp, const double* P,
+                                        const double* s, int64_t N, int64_t Npad, double c, double* Ms, int64_t ldm,
+                                        hipStream_t st) {
+  if (K < 1 || K > 16 || l < 0 || l >= K || N < 1 || (ldm & 1)) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)ceil_div(N + 1, 512), (unsigned)ceil_div(N, MSA_ROWS));
+  hipLaunchKernelGGL(multi_sample_assemble_kernel, grid, dim3(256), 0, st, loss, K, l, Ps, ldp, P, s, N, Npad, c, Ms,
+                     ldm);
+  return hipGetLastError();
+}
+
+// What the column blocks leave: one workgroup per row r of the padded system.  r < n = N·K: the last
+// column Σ_l Q_i[k,l] u_l[i] (l ascending), the zero padding columns, b[r] = R_ik; r = n: e_n and
+// b = 1; r > n: zeros.  u and R are N x K with stride Npad.
+__global__ __launch_bounds__(128) void multi_sample_tail_kernel(int loss, int K, const double* __restrict__ P,
+                                                                const double* __restrict__ sv,
+                                                                const double* __restrict__ u,
+                                                                const double* __restrict__ R, int64_t N, int64_t Npad,
+                                                                double c, double* __restrict__ Ms, int64_t ldm,
+                                                                double* __restrict__ b) {
+  const int64_t r = blockIdx.x, n = N * K;
+  double* row = Ms + r * ldm;
+  if (r < n) {
+    const int64_t k = r / N, i = r - k * N;
+    if (threadIdx.x == 0) {
+      double acc = 0.0;
+      for (int l = 0; l < K; ++l) acc += multi_q_entry(loss, P, sv, (int)k, l, i, Npad, c) * u[(int64_t)l * Npad + i];
+      row[n] = acc;
+      b[r] = R[k * Npad + i];
+    }
+    for (int64_t j = n + 1 + threadIdx.x; j < ldm; j += blockDim.x) row[j] = 0.0;
+  } else {
+    for (int64_t j = threadIdx.x; j < ldm; j += blockDim.x) row[j] = (r == n && j == n) ? 1.0 : 0.0;
+    if (threadIdx.x == 0) b[r] = (r == n) ? 1.0 : 0.0;
+  }
+}
+
+hipError_t launch_multi_sample_tail(int loss, int K, const double* P, const double* s, const double* u,
+                                    const double* R, int64_t N, int64_t Npad, double c, double* Ms, int64_t ldm,
+                                    double* b, hipStream_t st) {
+  if (K < 1 || K > 16 || N < 1 || ldm < N * K + 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(multi_sample_tail_kernel, dim3((unsigned)ldm), dim3(128), 0, st, loss, K, P, s, u, R, N, Npad, c,
+                     Ms, ldm, b);
+  return hipGetLastError();
+}
+
+// V[i + Npad*l] = B[i + N*l] (rows N..Npad zero): the solution's first N·K entries as the N x K
+// operand of Aᵀ V
+__global__ void multi_sample_spread_kernel(const double* __restrict__ B, int64_t N, int64_t Npad, int K,
+                                           double* __restrict__ V) {
+  const int64_t o = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (o >= Npad * K) return;
+  const int64_t l = o / Npad, i = o - l * Npad;
+  V[o] = (i < N) ? B[i + N * l] : 0.0;
+}
+
+hipError_t launch_multi_sample_spread(const double* B, int64_t N, int64_t Npad, int K, double* V, hipStream_t st) {
+  hipLaunchKernelGGL(multi_sample_spread_kernel, dim3((unsigned)ceil_div(Npad * K, 256)), dim3(256), 0, st, B, N, Npad,
+                     K, V);
+  return hipGetLastError();
+}
+
+// d[j + d*l] = -(h_l[j] t[j + d*l] + hg[j + d*l] B[n]), t = vec(Aᵀ V) (the single-output direction's form)
+__global__ void multi_sample_direction_kernel(const double* __restrict__ hP, const double* __restrict__ t,
+                                              const double* __restrict__ hg, const double* __restrict__ B, int64_t n,
+                                              int64_t d, int64_t dpad, int K, double* __restrict__ dir) {
+  const int64_t f = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (f >= d * K) return;
+  const int64_t l = f / d, j = f - l * d;
+  dir[f] = -(hP[l * dpad + j] * t[f] + hg[f] * B[n]);
+}
+
+hipError_t launch_multi_sample_direction(const double* hP, const double* t, const double* hg, const double* B,
+                                         int64_t n, int64_t d, int64_t dpad, int K, double* dir, hipStream_t st) {
+  hipLaunchKernelGGL(multi_sample_direction_kernel, dim3((unsigned)ceil_div(d * K, 256)), dim3(256), 0, st, hP, t, hg, B,
+                     n, d, dpad, K, dir);
   return hipGetLastError();
 }
 

@@ -96,6 +96,9 @@ struct scs_ctx : ViewData {
   // K-column blocked copies, 0 K launches of the single-vector product on the single-vector copies
   int sparse_outputs = 0;
   int ms_kernel = 0;
+  // scs_set_multi_sample: with nout set, ProxGGNSCORE at N·K + 1 <= d·K runs the sample-space branch
+  // (multi_sample_direction) instead of being refused (stored without effect while nout is unset)
+  int multi_sample = 0;
   double* mXt = nullptr;   // x = vec(X) repacked K-contiguous (dcp x K, zero beyond dc): launch_multi_pack_x
   double* mVt = nullptr;   // an N x K operand of Aᵀ V repacked K-contiguous (grow-only, mVt_cap doubles)
   int64_t mVt_cap = 0;
@@ -2677,6 +2680,40 @@ void sparse_sample_gram(scs_ctx* c, const double* h, double* Ps, int64_t NpS) {
   c->gram_kname = sparse_sample_kernel_name(c->sp_f32, B.nnz);
 }
 
+// The sample-space system M B = b solved in place (Ms row-major, order n1, padded order np1; bS <- B):
+// a non-finite system gives a NaN solution, the reference-solver mode runs the QR, else the LU with
+// `rebuild` (the system assembled again) as its redo.  Under T_SOLVE.
+template <class F>
+void sample_space_solve(scs_ctx* c, double* Ms, int64_t np1, int64_t n1, double* bS, F&& rebuild) {
+  hipEvent_t e0;
+  tbegin(c, T_SOLVE, &e0);
+  int info = 0;
+  // NaN / Inf in the system: the reference's qr(...) \ b comes out NaN (no SingularException)
+  HCK(hipMemsetAsync(c->cinfo, 0, sizeof(int), c->st));
+  HCK(launch_nonfinite(Ms, np1, n1, bS, c->cinfo, c->st));
+  HCK(hipMemcpyAsync(&info, c->cinfo, sizeof(int), hipMemcpyDeviceToHost, c->st));
+  sync(c);
+  if (info != 0) {
+    HCK(launch_fill(bS, n1, std::numeric_limits<double>::quiet_NaN(), c->st));
+  } else if (c->solver == SCS_SOLVER_REFERENCE) {
+    // qr(I + A) \ residual (prox-GGN-SCORE.jl:126): the row-major system transposed into a
+    // column-major copy with identity padding, Householder QR
+    if (c->qrM_n != np1) {
+      dfree_t(c, c->qrM);
+      c->qrM = dalloc<double>(c, (size_t)np1 * np1);
+      c->qrM_n = np1;
+    }
+    HCK(qr_from_rowmajor(Ms, np1, c->qrM, np1, n1, np1, c->st));
+    qr_run(c, &c->qr, c->qbk, c->qbk_n, c->qrM, np1, bS);
+  } else {
+    HCK(lu_aux_init(&c->lu, np1, c->st));
+    info = lu_factor_checked(c, Ms, np1, n1, np1, c->cinfo, rebuild);
+    if (info != 0) fail(c, SCS_ERR_SOLVE, "SingularException(%d)", info);
+    HCK(lu_solve(Ms, np1, np1, &c->lu, bS, c->st));
+  }
+  tend(c, T_SOLVE, e0);
+}
+
 void ggn_sample_direction(scs_ctx* c, const double* xh) {
   const int64_t N = c->N, m = c->m;
   if (sharded(c)) return ggn_sample_direction_sharded(c, xh);
@@ -2725,36 +2762,10 @@ void ggn_sample_direction(scs_ctx* c, const double* xh) {
                       uN, nullptr, nullptr, nullptr, nullptr, c->valpart, c->st));
   HCK(launch_ggn_sample_assemble(Ps, NpS, c->gN, c->hN, c->wN, uN, nullptr, N, Ms, n1pad, bS,
                                       c->st));
-  tbegin(c, T_SOLVE, &e0);
-  const int64_t n1 = N + 1, np1 = n1pad;
-  int info = 0;
-  // NaN / Inf in the system: the reference's qr(...) \ b comes out NaN (no SingularException)
-  HCK(hipMemsetAsync(c->cinfo, 0, sizeof(int), c->st));
-  HCK(launch_nonfinite(Ms, np1, n1, bS, c->cinfo, c->st));
-  HCK(hipMemcpyAsync(&info, c->cinfo, sizeof(int), hipMemcpyDeviceToHost, c->st));
-  sync(c);
-  if (info != 0) {
-    HCK(launch_fill(bS, n1, std::numeric_limits<double>::quiet_NaN(), c->st));
-  } else if (c->solver == SCS_SOLVER_REFERENCE) {
-    // qr(I + A) \ residual (prox-GGN-SCORE.jl:126): the row-major system transposed into a
-    // column-major copy with identity padding, Householder QR
-    if (c->qrM_n != np1) {
-      dfree_t(c, c->qrM);
-      c->qrM = dalloc<double>(c, (size_t)np1 * np1);
-      c->qrM_n = np1;
-    }
-    HCK(qr_from_rowmajor(Ms, np1, c->qrM, np1, n1, np1, c->st));
-    qr_run(c, &c->qr, c->qbk, c->qbk_n, c->qrM, np1, bS);
-  } else {
-    HCK(lu_aux_init(&c->lu, np1, c->st));
-    info = lu_factor_checked(c, Ms, np1, n1, np1, c->cinfo, [&] {   // the system assembled again
-      HCK(launch_ggn_sample_assemble(Ps, NpS, c->gN, c->hN, c->wN, uN, nullptr, N, Ms, n1pad, bS,
-                                     c->st));
-    });
-    if (info != 0) fail(c, SCS_ERR_SOLVE, "SingularException(%d)", info);
-    HCK(lu_solve(Ms, np1, np1, &c->lu, bS, c->st));
-  }
-  tend(c, T_SOLVE, e0);
+  sample_space_solve(c, Ms, n1pad, N + 1, bS, [&] {   // the system assembled again
+    HCK(launch_ggn_sample_assemble(Ps, NpS, c->gN, c->hN, c->wN, uN, nullptr, N, Ms, n1pad, bS,
+                                   c->st));
+  });
   HCK(launch_ggn_sample_scale(c->gN, bS, N, c->Npad, c->vN, c->st));
   gemv_t_local(c, c->vN, c->gtmp);   // Aᵀ(s∘B)
   HCK(launch_ggn_sample_direction(hvec, c->gtmp, hg, bS, N, m, c->d, c->st));
@@ -2838,13 +2849,25 @@ static void clear_gram_padding(scs_ctx* c) {
 
 // ProxGGNSCORE on a multi-output context takes the feature branch only: with N·K + 1 <= d·K the
 // reference's sample-space branch (prox-GGN-SCORE.jl:124-127) gives another step
+bool multi_sample_shape(const scs_ctx* c) { return multi(c) && c->Nglob * c->nout + 1 <= c->m; }
+
+// ... unless scs_set_multi_sample is on: multi_sample_direction then runs that branch on a dense A
 void refuse_multi_sample_space(scs_ctx* c, int method) {
-  if (multi(c) && method == SCS_PROX_GGNSCORE && c->Nglob * c->nout + 1 <= c->m)
-    fail(c, SCS_ERR_ARG, "ProxGGNSCORE with scs_set_outputs (nout = %d): N*nout + 1 = %lld <= d*nout = %lld, where the "
-                         "reference takes its sample-space branch (H^-1 = 1/Hr without lambda: another step); the "
-                         "multi-output device path forms the feature branch only -- use the callback loss "
-                         "(losses.callback) for this shape", c->nout, (long long)(c->Nglob * c->nout + 1),
-         (long long)c->m);
+  if (!multi_sample_shape(c) || method != SCS_PROX_GGNSCORE) return;
+  if (c->multi_sample) {
+    if (c->sparse)
+      fail(c, SCS_ERR_ARG, "ProxGGNSCORE with scs_set_outputs (nout = %d) at N*nout + 1 = %lld <= d*nout = %lld: the "
+                           "sample-space branch of multi_sample / scs_set_multi_sample needs a dense A (a sparse A, "
+                           "scs_set_sparse_outputs included, is not supported there) -- use the callback loss "
+                           "(losses.callback) for this shape", c->nout, (long long)(c->Nglob * c->nout + 1),
+           (long long)c->m);
+    return;
+  }
+  fail(c, SCS_ERR_ARG, "ProxGGNSCORE with scs_set_outputs (nout = %d): N*nout + 1 = %lld <= d*nout = %lld, where the "
+                       "reference takes its sample-space branch (H^-1 = 1/Hr without lambda: another step); the "
+                       "multi-output device path forms the feature branch only -- use the callback loss "
+                       "(losses.callback) for this shape", c->nout, (long long)(c->Nglob * c->nout + 1),
+       (long long)c->m);
 }
 
 // The order-d·K system of a multi-output loss at the point of the last forward(EPI_GGN) (P in hN, s in
@@ -2874,6 +2897,90 @@ void multi_system(scs_ctx* c) {
   tend(c, T_GRAM, e0);
 }
 
+// ---- ProxGGNSCORE's sample-space branch of a multi-output loss (scs_set_multi_sample) ----
+// The view's sample-space fields hold its data: At the d-column transpose (NpS x dcp), ss.Ps one N x N
+// P_l at a time, ss.Ms the row-major system of order N·K + 1, ss.uN the K vectors u_l (then V),
+// ss.hvec the K padded weight slices h_l (dcp each), ss.hg = h ∘ λ gr in vec layout.
+void multi_sample_setup(scs_ctx* c) {
+  if (c->At) return;
+  if (c->sparse) fail(c, SCS_ERR_ARG, "the multi-output sample-space branch (multi_sample) needs a dense A");
+  free_buffers(c, *c, VB_SAMPLE);   // (what an allocation that failed half way left)
+  c->nstiles = 0;
+  const int64_t N = c->N, K = c->nout;
+  SampleSys& O = c->ss;
+  O.N = N;
+  O.NpS = round_up(N, 128);
+  O.n1pad = round_up(N * K + 1, 128);   // row-major, zero padding (lu.hip)
+  O.Ps = dalloc<double>(c, (size_t)O.NpS * O.NpS);
+  O.Ms = dalloc<double>(c, (size_t)O.n1pad * O.n1pad);
+  O.bS = dalloc<double>(c, O.n1pad);
+  O.uN = dalloc<double>(c, (size_t)c->Npad * K);
+  O.hvec = dalloc<double>(c, (size_t)c->dcp * K);
+  O.hg = dalloc<double>(c, c->mpad);
+  const int nb = (int)(O.NpS / 128);
+  std::vector<int2> tl((size_t)nb * (nb + 1) / 2);
+  int nt = 0;
+  gram_tile_list(nb, tl.data(), &nt);
+  c->stiles = dalloc<int2>(c, nt);
+  HCK(hipMemcpyAsync(c->stiles, tl.data(), sizeof(int2) * nt, hipMemcpyHostToDevice, c->st));
+  c->nstiles = nt;
+  double* At = dalloc<double>(c, (size_t)O.NpS * c->dcp);
+  HCK(launch_transpose(c->A, c->a32, c->Npad, N, c->dc, At, c->dcp, O.NpS, c->st));
+  sync(c);   // (the tile list's host copy goes out of scope)
+  c->At = At;
+}
+
+// The column blocks of the system at the point of the last forward(EPI_GGN): per l the Gram P_l (the
+// single-output launch on At with the weights h_l), its mirror, one assembly launch; then the tail.
+// time_asm (the door): the assembly and tail launches are bracketed under T_STEP, which no step is using
+void multi_sample_assemble(scs_ctx* c, bool time_asm = false) {
+  const SampleSys& S = c->ss;
+  const int K = c->nout;
+  hipEvent_t e0;
+  for (int l = 0; l < K; ++l) {
+    tbegin(c, T_GRAM, &e0);
+    HCK(gram_launch_gen(c->At, c->dcp, c->At, c->dcp, S.hvec + (int64_t)l * c->dcp, 0, c->dcp, c->stiles, c->nstiles,
+                        S.Ps, S.NpS, /*GRAM_UPPER*/ 4, c->st));
+    tend(c, T_GRAM, e0);
+    HCK(launch_symmetrize(S.Ps, S.NpS, c->N, c->st));
+    if (time_asm) tbegin(c, T_STEP, &e0);
+    HCK(launch_multi_sample_assemble(c->loss, K, l, S.Ps, S.NpS, c->hN, c->vN, c->N, c->Npad, c->scale, S.Ms, S.n1pad,
+                                     c->st));
+    if (time_asm) tend(c, T_STEP, e0);
+  }
+  if (time_asm) tbegin(c, T_STEP, &e0);
+  HCK(launch_multi_sample_tail(c->loss, K, c->hN, c->vN, S.uN, c->gN, c->N, c->Npad, c->scale, S.Ms, S.n1pad, S.bS,
+                               c->st));
+  if (time_asm) tend(c, T_STEP, e0);
+}
+
+// forward pass (P -> hN, s -> vN, R -> gN), h and h ∘ λ gr, the K vectors u_l in one pass over A, the system
+void multi_sample_system(scs_ctx* c, const double* xh, bool time_asm = false) {
+  multi_sample_setup(c);
+  const SampleSys& S = c->ss;
+  const int K = c->nout;
+  forward(c, xh, c->x, EPI_GGN, false);
+  HCK(launch_multi_sample_prep(c->Hr, c->gr, c->lam, c->dc, c->dcp, K, S.hvec, S.hg, c->st));
+  hipEvent_t e0;
+  tbegin(c, T_GEMV, &e0);
+  const int ns = matvec_n(c, S.hg, c->nsplit);   // U = A reshape(h ∘ λ gr, d, K)
+  tend(c, T_GEMV, e0);
+  HCK(launch_multi_epilogue(SCS_LOSS_MULTI_LS, EPI_Z, K, c->zpart, ns, nullptr, c->N, c->Npad, 1.0, S.uN, nullptr,
+                            nullptr, nullptr, nullptr, c->st));
+  multi_sample_assemble(c, time_asm);
+}
+
+void multi_sample_direction(scs_ctx* c, const double* xh) {
+  multi_sample_system(c, xh);
+  const SampleSys& S = c->ss;
+  const int K = c->nout;
+  const int64_t n = c->N * K;
+  sample_space_solve(c, S.Ms, S.n1pad, n + 1, S.bS, [&] { multi_sample_assemble(c); });
+  HCK(launch_multi_sample_spread(S.bS, c->N, c->Npad, K, S.uN, c->st));
+  gemv_t_local(c, S.uN, c->gtmp);   // vec(Aᵀ V), V = reshape(B[0 : N·K], N, K): one pass over A
+  HCK(launch_multi_sample_direction(S.hvec, c->gtmp, S.hg, S.bS, n, c->dc, c->dcp, K, c->d, c->st));
+}
+
 // ProxNSCORE / ProxGGNSCORE direction of a multi-output loss -> c->d.  ∇²f = JᵀQJ (J = I_K ⊗ A, the
 // output is linear in x), so both methods build the same system; rhs = vec(AᵀR) + λ gr.
 void multi_newton_direction(scs_ctx* c, const double* xh) {
@@ -2881,6 +2988,7 @@ void multi_newton_direction(scs_ctx* c, const double* xh) {
   refuse_multi_sample_space(c, c->method);
   if (c->method == SCS_PROX_GGNSCORE && c->ggn == SCS_GGN_NONE)
     fail(c, SCS_ERR_ARG, "ProxGGNSCORE needs an out_fn / GGN loss kind");
+  if (c->method == SCS_PROX_GGNSCORE && multi_sample_shape(c)) return multi_sample_direction(c, xh);
   forward(c, xh, c->x, EPI_GGN, false);
   gemv_t_local(c, c->gN, c->gtmp);
   if (c->gfix && c->method == SCS_PROX_NSCORE) grad_f_dev(c, xh, c->x, c->gtmp);
@@ -5700,6 +5808,28 @@ int scs_set_sparse_outputs(scs_ctx* c, int on) {
   return guarded(c, [&] { c->sparse_outputs = on ? 1 : 0; });
 }
 
+// ProxGGNSCORE's sample-space branch with nout set (N·nout + 1 <= d·nout, a dense A): stored without
+// effect while nout is unset.  Switching it off with the data in place gives the branch's buffers back.
+int scs_set_multi_sample(scs_ctx* c, int on) {
+  if (!c) return SCS_ERR_ARG;
+  if (is_group(c)) {
+    c->err = "scs_set_multi_sample takes a single-device context (scs_create): a multi-device context "
+             "(devices=[...]) is not supported with nout";
+    return SCS_ERR_ARG;
+  }
+  return guarded(c, [&] {
+    const int v = on ? 1 : 0;
+    if (v == c->multi_sample) return;
+    c->multi_sample = v;
+    if (!v && multi(c) && c->has_data && !c->sparse && c->At) {
+      HCK(hipSetDevice(c->dev));
+      sync(c);
+      free_buffers(c, *c, VB_SAMPLE);
+      c->nstiles = 0;
+    }
+  });
+}
+
 // A X (N x K) and Aᵀ V (d x K) of host operands through multi.hip's kernels; K is the call's own.  A
 // sparse A held in the scs_set_sparse_outputs mode: through the context's own product arm, K = nout.
 int scs_multi_products_eval(scs_ctx* c, int K, const double* X, const double* V, double* AX, double* ATV) {
@@ -5796,6 +5926,56 @@ int scs_multi_system_eval(scs_ctx* c, const double* x, double* G, int64_t ldg, d
     if (g) d2h(c, g, c->gtmp, m);
     sync(c);
     if (f) *f = fv;
+    invalidate_caches(c);
+    if (c->timing) tresolve(c);
+  });
+}
+
+// the sample-space system of a multi-output ProxGGNSCORE step at x (the step's own forward pass and
+// assembly, before the solve): M of order n1 = N·nout + 1 and b
+int scs_multi_sample_system_eval(scs_ctx* c, const double* x, double* M, int64_t ldm, double* b) {
+  return guarded(c, [&] {
+    if (!c->has_data || c->generic) fail(c, SCS_ERR_STATE, "no data");
+    if (!multi(c))
+      fail(c, SCS_ERR_STATE, "scs_multi_sample_system_eval needs a multi-output context (scs_set_outputs)");
+    if (!c->multi_sample)
+      fail(c, SCS_ERR_STATE, "scs_multi_sample_system_eval needs the sample-space switch (multi_sample=True / "
+                             "scs_set_multi_sample)");
+    if (!c->loss_set) fail(c, SCS_ERR_STATE, "no loss: call scs_set_loss first");
+    if (!c->reg_set || !c->smooth_set)
+      fail(c, SCS_ERR_STATE, "scs_multi_sample_system_eval needs the regularizer and the smoother (h = 1 ./ Hr, λ gr)");
+    if (c->ggn == SCS_GGN_NONE) fail(c, SCS_ERR_ARG, "scs_multi_sample_system_eval needs an out_fn / GGN loss kind");
+    const int64_t n1 = c->Nglob * c->nout + 1;
+    if (!multi_sample_shape(c))
+      fail(c, SCS_ERR_ARG, "scs_multi_sample_system_eval: N*nout + 1 = %lld > d*nout = %lld is the feature branch's "
+                           "shape (scs_multi_system_eval serves it)", (long long)n1, (long long)c->m);
+    if (c->sparse)
+      fail(c, SCS_ERR_ARG, "scs_multi_sample_system_eval: the sample-space branch of multi_sample needs a dense A");
+    if (!x || (M && ldm < n1)) fail(c, SCS_ERR_ARG, "scs_multi_sample_system_eval: null x or ldm < N*nout + 1");
+    HCK(hipSetDevice(c->dev));
+    invalidate_caches(c);
+    h2d(c, c->x, x, c->m);
+    HCK(launch_smoother(c->smooth, c->x, c->m, c->mu, c->slb, c->sub, c->wel, c->gr, c->Hr, c->st));
+    multi_sample_system(c, x, true);
+    const SampleSys& S = c->ss;
+    // Ms is row-major: its transpose lands column-major on the host through a column-major staging copy
+    if (M) {
+      double* T = dalloc<double>(c, (size_t)S.n1pad * S.n1pad, false);
+      struct Free {
+        scs_ctx* c;
+        double** p;
+        ~Free() {
+          (void)hipStreamSynchronize(c->st);
+          dfree_t(c, *p);
+        }
+      } fr{c, &T};
+      HCK(qr_from_rowmajor(S.Ms, S.n1pad, T, S.n1pad, n1, S.n1pad, c->st));
+      HCK(hipMemcpy2DAsync(M, sizeof(double) * ldm, T, sizeof(double) * S.n1pad, sizeof(double) * n1, n1,
+                           hipMemcpyDeviceToHost, c->st));
+      sync(c);
+    }
+    if (b) d2h(c, b, S.bS, n1);
+    sync(c);
     invalidate_caches(c);
     if (c->timing) tresolve(c);
   });

@@ -16,7 +16,8 @@ import SelfConcordantSmoothOptimization: step!, init!, ProximalMethod, ProxModel
 
 export DeviceProblem, configure!, iterate_device!, set_gram_cache!, set_solver!, rccl_unique_id, set_comm_rccl!,
        set_comm_callback!, set_test!, set_test_device!, set_compute_f32!, fallback_counts, data_info, samplewise,
-       set_sparse_batches!, set_sparse_sample!, batch_info
+       set_sparse_batches!, set_sparse_sample!, batch_info, set_multi_sample!,
+       multi_sample_system
 
 const lib = joinpath(@__DIR__, "..", "scsopt", "libscsopt.so")
 
@@ -252,16 +253,19 @@ end
 # x0 = vec(X0) with X0 d x K, loss :softmax_ce (out_fn :linear_softmax_ce) or :multi_least_squares
 # (out_fn :linear_multi_ls).  scs_set_outputs goes before the data door, whose m is then A's column
 # count d; A stays on the device as one N x d block (Matrix{Float32}: stored as fp32).  One device, one
-# rank, the full batch; an Atest takes an Ntest x K ytest.
+# rank, the full batch; an Atest takes an Ntest x K ytest.  multi_sample = true: with N*K + 1 <= d*K
+# ProxGGNSCORE runs the reference's sample-space branch on the device instead of being refused
+# (scs_set_multi_sample).
 function DeviceProblem(A::Union{Matrix{Float64},Matrix{Float32}}, Y::AbstractMatrix, x0::Vector{Float64},
                        loss::Symbol, λ; out_fn::Union{Symbol,Nothing}=nothing, scale::Float64=1.0 / size(A, 1),
                        L=nothing, sol::Vector{Float64}=zero(x0), C_set=nothing, P=nothing, device::Integer=0,
-                       Atest=nothing, ytest=nothing)
+                       Atest=nothing, ytest=nothing, multi_sample::Bool=false)
     N, d = size(A)
     K = size(Y, 2)
     (size(Y, 1) == N && length(x0) == d * K) ||
         throw(DimensionMismatch("Y must be N x K and length(x0) = size(A, 2) * K"))
     ctx = create_ctx(device)
+    multi_sample && chk(ccall((:scs_set_multi_sample, lib), Cint, (Ptr{Cvoid}, Cint), ctx, 1), ctx)
     chk(ccall((:scs_set_outputs, lib), Cint, (Ptr{Cvoid}, Cint), ctx, K), ctx)
     Ym = Matrix{Float64}(Y)
     if A isa Matrix{Float32}
@@ -302,6 +306,25 @@ function multi_system(model::DeviceProblem, x::Vector{Float64})
               (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ref{Float64}),
               model.ctx, x, G, n, g, f), model.ctx)
     return G, g, f[]
+end
+
+# ProxGGNSCORE's sample-space branch of a multi-output problem (N*K + 1 <= d*K, a dense A) on or off
+# (scs_set_multi_sample; off by default: that shape is refused).  Stored without effect without nout.
+function set_multi_sample!(model::DeviceProblem, on::Bool=true)
+    chk(ccall((:scs_set_multi_sample, lib), Cint, (Ptr{Cvoid}, Cint), model.ctx, on ? 1 : 0), model.ctx)
+    return model
+end
+
+# (M, b) of the sample-space system a multi-output ProxGGNSCORE step solves at x (multi_sample = true;
+# the regularizer and the smoother set): M of order N*K + 1, rows and columns (i, k) = i + N*k
+function multi_sample_system(model::DeviceProblem, x::Vector{Float64})
+    K, _ = get_outputs(model)
+    n1 = size(model.y, 1) * K + 1
+    M = zeros(n1, n1); b = zeros(n1)
+    chk(ccall((:scs_multi_sample_system_eval, lib), Cint,
+              (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}),
+              model.ctx, x, M, n1, b), model.ctx)
+    return M, b
 end
 
 # A::Matrix{Float32} (A::DataTupleOrArray2 admits it, problems.jl:61-62; with x::Vector{Float64} Julia

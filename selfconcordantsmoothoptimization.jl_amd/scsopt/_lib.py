@@ -115,6 +115,7 @@ _SIGS = {
                                 C.POINTER(C.c_int), C.c_char_p, C.c_int64]),
     "scs_set_outputs": (C.c_int, [C.c_void_p, C.c_int]),
     "scs_set_sparse_outputs": (C.c_int, [C.c_void_p, C.c_int]),
+    "scs_set_multi_sample": (C.c_int, [C.c_void_p, C.c_int]),
     "scs_get_outputs": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), c_i64p]),
     "scs_set_data": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, c_dp, C.c_int64, c_dp, C.c_int64, C.c_int64]),
     "scs_gen_data": (C.c_int, [C.c_void_p, C.POINTER(Synth)]),
@@ -188,6 +189,7 @@ _SIGS = {
     "scs_gram_atv_eval": (C.c_int, [C.c_void_p, c_dp, c_dp, c_i64p, C.c_int64, c_dp, c_dp, C.POINTER(C.c_int)]),
     "scs_multi_products_eval": (C.c_int, [C.c_void_p, C.c_int, c_dp, c_dp, c_dp, c_dp]),
     "scs_multi_system_eval": (C.c_int, [C.c_void_p, c_dp, c_dp, C.c_int64, c_dp, c_dp]),
+    "scs_multi_sample_system_eval": (C.c_int, [C.c_void_p, c_dp, c_dp, C.c_int64, c_dp]),
     "scs_timing_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "scs_timing_get": (C.c_int, [C.c_void_p, C.POINTER(Timing)]),
     "scs_timing_reset": (C.c_int, [C.c_void_p]),

@@ -96,7 +96,8 @@ class Problem:
     def __init__(self, *args, Atest=None, ytest=None, L=None, sol=None, C_set=None, P=None,
                  out_fn: Optional[OutFn] = None, name=None, device=0, comm=None, N_global=None, row0=0,
                  sparse_f32=False, devices=None, device_exchange="rccl", Ntest_global=None, test_row0=0,
-                 dense_f32=False, sparse_batches=False, sparse_sample=False, sparse_outputs=False, _ctx=None):
+                 dense_f32=False, sparse_batches=False, sparse_sample=False, sparse_outputs=False, multi_sample=False,
+                 _ctx=None):
         if len(args) == 5:
             A, y, x0, f, lam = args
         elif len(args) == 3:
@@ -123,6 +124,14 @@ class Problem:
         # sparse_outputs: a multi-output loss on a sparse A (scipy matrix or device CSR) -- the products run
         # with nout right-hand sides in one pass over the nonzeros (scs_set_sparse_outputs)
         self.sparse_outputs = bool(sparse_outputs)
+        # multi_sample: with nout set and N·nout + 1 <= d·nout, ProxGGNSCORE runs the reference's sample-space
+        # branch on the device (a dense A) instead of being refused (scs_set_multi_sample)
+        if not isinstance(multi_sample, (bool, np.bool_)):
+            raise TypeError(f"multi_sample must be a bool, got {type(multi_sample).__name__}")
+        self.multi_sample = bool(multi_sample)
+        if self.multi_sample and devices is not None:
+            raise ValueError("multi_sample=True takes a single-device context: devices=[...] is not supported with "
+                             "nout")
         self.nout = self._check_outputs(f, out_fn, A, comm, devices, _ctx)
         self.d = self.m // self.nout   # A's columns
         if f.kind == "callback":   # the data stays with the caller's closures; the device holds none
@@ -149,6 +158,8 @@ class Problem:
             self.ctx.check(_lib.lib.scs_set_sparse_sample(self.ctx.h, 1))
         if self.sparse_outputs:   # a mode of the context: inert without nout
             self.ctx.check(_lib.lib.scs_set_sparse_outputs(self.ctx.h, 1))
+        if self.multi_sample:     # likewise inert without nout
+            self.ctx.check(_lib.lib.scs_set_multi_sample(self.ctx.h, 1))
         if self.nout > 1:   # before the data door: its m is then A's column count d, y is N x nout
             self.ctx.check(_lib.lib.scs_set_outputs(self.ctx.h, self.nout))
         if comm is not None and comm.active and _ctx is None:
@@ -849,6 +860,13 @@ class Problem:
         drops the pooled views.  scs_set_sparse_sample."""
         self.ctx.check(_lib.lib.scs_set_sparse_sample(self.ctx.h, int(bool(on))))
 
+    def set_multi_sample(self, on=True):
+        """Opt-in: with nout set and N·nout + 1 <= d·nout, ProxGGNSCORE runs the reference's sample-space branch
+        on the device (a dense A): K Grams A diag(h_l) Aᵀ, the order-(N·nout + 1) block system, one LU.  Off: that
+        shape is refused.  Stored without effect while nout is unset.  scs_set_multi_sample."""
+        self.ctx.check(_lib.lib.scs_set_multi_sample(self.ctx.h, int(bool(on))))
+        self.multi_sample = bool(on)
+
     def batch_info(self):
         """(sparse batch views held, their device bytes, views built since set_batches) -- scs_batch_info."""
         nv, vb, bd = C.c_int64(), C.c_int64(), C.c_int64()
@@ -947,6 +965,20 @@ class Problem:
         self.ctx.check(_lib.lib.scs_multi_system_eval(self.ctx.h, dptr(x), C.cast(G.ctypes.data, _lib.c_dp), self.m,
                                                       dptr(g), C.byref(f)))
         return G, g, f.value
+
+    def multi_sample_system(self, x):
+        """(M, b) of the sample-space system a multi-output ProxGGNSCORE step solves at x (multi_sample=True,
+        N·nout + 1 <= d·nout; configure() first: h = 1 ./ Hr and λ gr enter it) -- M of order N·nout + 1, rows and
+        columns (i, k) = i + N·k, by the step's own forward pass and assembly (scs_multi_sample_system_eval)."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.shape != (self.m,):
+            raise ValueError(f"x must have length d * nout = {self.m}")
+        n1 = self.N * self.nout + 1
+        Mm = np.zeros((n1, n1), order="F")
+        b = np.empty(n1)
+        self.ctx.check(_lib.lib.scs_multi_sample_system_eval(self.ctx.h, dptr(x), C.cast(Mm.ctypes.data, _lib.c_dp), n1,
+                                                             dptr(b)))
+        return Mm, b
 
     def get_columns(self, cols):
         """Columns of the local A (N x len(cols), float64)."""
