@@ -262,10 +262,10 @@ int scs_set_loss_samplewise(scs_ctx* ctx, scs_samplewise_fn* fn, void* user, int
  * Refused with SCS_ERR_ARG: nout outside 2..16 (nout = 0 clears the mode); with nout set: a
  * sparse A (scs_set_sparse*, scs_set_test_sparse*) unless scs_set_sparse_outputs is on (below),
  * scs_gen_sparse, scs_gen_data, scs_set_compute_f32, nranks > 1 and multi-device contexts,
- * scs_set_batches, any other loss kind, and ProxGGNSCORE when N*nout + 1 <= d*nout (the reference
- * then takes its sample-space branch, whose step differs: scs_set_multi_sample below runs it on a
- * dense A; without it use the callback loss).  The mode persists across data doors, as
- * scs_set_dense_f32 does.                                                                        */
+ * scs_set_batches unless scs_set_multi_batches is on (below: a dense A), any other loss kind, and
+ * ProxGGNSCORE when N*nout + 1 <= d*nout (the reference then takes its sample-space branch, whose
+ * step differs: scs_set_multi_sample below runs it on a dense A; without it use the callback
+ * loss).  The mode persists across data doors, as scs_set_dense_f32 does.                        */
 /* (With nout set scs_get_dims reports A's column count d as m, scs_get_data returns y as nr x nout
  * with leading dimension nr, and the single-vector kernel-level doors -- scs_gemv_n_eval,
  * scs_gemv_t_eval, scs_gram_eval, scs_solve_eval, scs_gram_atv_eval, scs_sample_gram_eval -- are
@@ -302,6 +302,21 @@ int scs_set_sparse_outputs(scs_ctx* ctx, int on);
  * sparse A (scs_set_sparse_outputs included) -- the branch needs a dense A.  Refused on multi-device
  * contexts as scs_set_outputs is.                                                                  */
 int scs_set_multi_sample(scs_ctx* ctx, int on);
+/* Minibatches of a multi-output loss (opt-in; off by default: scs_set_batches then refuses a context
+ * with nout set).  With the switch on and nout = K set, scs_set_batches accepts a context that holds
+ * a dense A (fp64 or fp32 storage, the host or the device door): scs_select_batch gathers the
+ * batch's n_b rows of A (the d-column view, the source's element type) and of Y (n_b x K) into a
+ * pooled view in one launch, and a step on it is the step of a context holding A[rows_b],
+ * Y[rows_b].  f, get_reg, the histories and the held-out loss stay on the full data.  ProxGGNSCORE
+ * picks its branch per batch: n_b*K + 1 > d*K the feature branch, otherwise the sample-space branch
+ * with scs_set_multi_sample on and its refusal (raised at that batch's step, naming n_b) with it
+ * off.  SCS_MULTI_GATHER=0 (read at scs_set_batches) gathers with the single-output kernel over the
+ * d-column view plus one launch per further target column instead: the same bits.  A sparse A
+ * (scs_set_sparse_outputs included) stays refused at scs_set_batches: a dense A is needed.  Stored
+ * without effect while nout is unset; changing it drops the pooled batch views, and switching it
+ * off with a list registered on a multi-output context clears the list.  Refused on multi-device
+ * contexts as scs_set_outputs is.                                                                  */
+int scs_set_multi_batches(scs_ctx* ctx, int on);
 
 /* ---- data  (Problem(A, y, ...) -- problems.jl:61-81) --------------------- */
 /* Upload host A (column-major, N x m, leading dim lda) and y (N).  N is the
@@ -533,6 +548,12 @@ int scs_eval_reg(scs_ctx* ctx, const double* x, double* gval);
  * scs_set_sparse_batches keeps them sparse.                                 */
 int scs_set_batches(scs_ctx* ctx, const int64_t* rows, const int64_t* offsets, int64_t nbatch);
 int scs_select_batch(scs_ctx* ctx, int64_t b);
+/* Batch b of the registered list as a step sees it, gathered by scs_select_batch's own path: its
+ * n_b x d rows widened to fp64 into A_out (column-major, leading dimension lda >= n_b; NULL skips
+ * them) and its targets into Y_out (n_b, or n_b x nout column-major with leading dimension n_b;
+ * NULL skips them).  A dense batch view only (a batch held as a sparse view under
+ * scs_set_sparse_batches is refused); single-device contexts; the selection is left as found.    */
+int scs_get_batch_data(scs_ctx* ctx, int64_t b, double* A_out, int64_t lda, double* Y_out);
 /* Opt-in (default 0): under ProxLQNSCORE a minibatch of a sparse A stays sparse.  scs_select_batch
  * then builds a sparse view instead of the n_b x m_pad dense one: bit for bit the two blocked
  * copies scs_set_sparse would build from A[rows_b, :] (rows in batch order, a repeated row kept

@@ -458,6 +458,15 @@ hipError_t launch_multi_sample_tail(int loss, int K, const double* P, const doub
 hipError_t launch_multi_sample_spread(const double* B, int64_t N, int64_t Npad, int K, double* V, hipStream_t st);
 hipError_t launch_multi_sample_direction(const double* hP, const double* t, const double* hg, const double* B,
                                          int64_t n, int64_t d, int64_t dpad, int K, double* dir, hipStream_t st);
+// a minibatch of a multi-output context (scs_set_multi_batches): rows[0..n) of the panel-blocked A (Npad x dpad)
+// and of Y (N x K, stride ldy) -> Ab (Npad_b x dpad, A's element type) and Yb (stride Npad_b), rows
+// n..Npad_b zero in both -- one launch; the same bits as launch_gather_rows over dpad columns plus
+// launch_gather_y per column
+// the default arm of that gather (1: this kernel, 0: the launches it replaces), as measured
+int multi_gather_default(int a32);
+hipError_t launch_multi_gather_rows(const void* A, int a32, int64_t Npad, int64_t dpad, const double* Y, int64_t ldy,
+                                    int K, const int64_t* rows, int64_t n, int64_t Npad_b, void* Ab, double* Yb,
+                                    hipStream_t st);
 
 // ---- multi_sparse.hip: the same two products on a sparse A (scs_set_sparse_outputs), one pass over the
 // nonzeros for all K columns.  The blocked copy is build_blocked's at shift multi_spmm_shift(ncols, K)

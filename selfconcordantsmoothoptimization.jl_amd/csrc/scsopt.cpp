@@ -99,6 +99,12 @@ struct scs_ctx : ViewData {
   // scs_set_multi_sample: with nout set, ProxGGNSCORE at N·K + 1 <= d·K runs the sample-space branch
   // (multi_sample_direction) instead of being refused (stored without effect while nout is unset)
   int multi_sample = 0;
+  // scs_set_multi_batches: with nout set, scs_set_batches accepts a dense A instead of refusing (stored
+  // without effect while nout is unset).  mb_gather: the arm read where the list is registered
+  // (multi_gather_arm): 1 multi.hip's one-launch gather, 0 gather_rows_kernel over dcp columns plus one
+  // launch_gather_y per further target column
+  int multi_batches = 0;
+  int mb_gather = 1;
   double* mXt = nullptr;   // x = vec(X) repacked K-contiguous (dcp x K, zero beyond dc): launch_multi_pack_x
   double* mVt = nullptr;   // an N x K operand of Aᵀ V repacked K-contiguous (grow-only, mVt_cap doubles)
   int64_t mVt_cap = 0;
@@ -1328,7 +1334,7 @@ void select_batch(scs_ctx* c, int64_t b) {
     v.nstage = v.Npad / 16;
     v.a32 = c->sparse ? 0 : c->a32;   // a batch of an fp32-stored A is fp32; the dense batch of a sparse A fp64
     v.A = alloc_A(c, v.Npad, v.a32);
-    v.y = dalloc<double>(c, v.Npad);
+    v.y = dalloc<double>(c, v.Npad * kout(c));   // a multi-output view: Y_b, n_b x K with stride Npad_b
     alloc_nspace(c, v);
     c->bpool.push_back(v);
     c->bheld.push_back(-1);
@@ -1339,7 +1345,17 @@ void select_batch(scs_ctx* c, int64_t b) {
     ++c->y_stamp;   // the view's y is gathered again
     if (n == 0) {
       HCK(hipMemsetAsync(v.A, 0, a_block_bytes(c, v.Npad, v.a32), c->st));
-      HCK(hipMemsetAsync(v.y, 0, sizeof(double) * v.Npad, c->st));
+      HCK(hipMemsetAsync(v.y, 0, sizeof(double) * v.Npad * kout(c), c->st));
+    } else if (multi(c)) {   // scs_set_multi_batches (a dense A): dcp columns and the K target columns
+      const int64_t* rows = c->brows + c->boff[b];
+      if (c->mb_gather) {
+        HCK(launch_multi_gather_rows(c->A, c->a32, c->Npad, c->dcp, c->y, c->Npad, c->nout, rows, n, v.Npad, v.A, v.y,
+                                     c->st));
+      } else {
+        HCK(launch_gather_rows(c->A, c->a32, c->Npad, c->y, rows, n, v.Npad, c->dcp, v.A, v.a32, v.y, c->st));
+        for (int l = 1; l < c->nout; ++l)
+          HCK(launch_gather_y(c->y + (int64_t)l * c->Npad, rows, n, v.Npad, v.y + (int64_t)l * v.Npad, c->st));
+      }
     } else if (c->sparse) {   // CSR rows -> the dense batch (the reference's Matrix(As') of a sparse A)
       HCK(hipMemsetAsync(v.A, 0, sizeof(double) * (size_t)v.Npad * c->mpad, c->st));
       HCK(launch_densify_rows(c->rowptr, c->colidx, c->val, c->sp_f32, c->brows + c->boff[b], n, v.Npad, c->y,
@@ -1349,7 +1365,8 @@ void select_batch(scs_ctx* c, int64_t b) {
                              c->st));
     }
     // the view's GGN sample-space Aᵀ copy (built once per A, ggn_sample_step) follows its rows
-    if (v.At) HCK(launch_transpose(v.A, v.a32, v.Npad, n, c->m, v.At, c->mpad, v.ss.NpS, c->st));
+    // (a multi-output view's copy has the data view's dc columns: multi_sample_setup)
+    if (v.At) HCK(launch_transpose(v.A, v.a32, v.Npad, n, c->dc, v.At, c->dcp, v.ss.NpS, c->st));
     c->bheld[k] = b;
   }
   c->bview = k;
@@ -3425,6 +3442,16 @@ static int multi_sparse_arm(int K, int f32) {
   return multi_spmm_default(K, f32);
 }
 
+// The gather of a multi-output context's batches (scs_set_multi_batches): 1 multi.hip's one-launch kernel,
+// 0 gather_rows_kernel over dcp columns plus launch_gather_y per further target column.  Both write the
+// same bits.  SCS_MULTI_GATHER=0 / 1 forces an arm (read where the list is registered); the default is
+// the measured one per storage type (multi_gather_default in multi.hip, the one place of the rule;
+// DESIGN §2k).
+static int multi_gather_arm(int a32) {
+  if (const char* e = std::getenv("SCS_MULTI_GATHER")) return e[0] != '0';
+  return multi_gather_default(a32);
+}
+
 static void set_dims(scs_ctx* c, int64_t N, int64_t m, int64_t Nglob, int64_t row0) {
   if (m <= 0 || N < 0) fail(c, SCS_ERR_ARG, "bad dimensions N=%lld m=%lld", (long long)N, (long long)m);
   c->N = N;
@@ -3847,30 +3874,36 @@ int scs_gen_data(scs_ctx* c, const scs_synth* s) {
   });
 }
 
+// rows [r0, r0 + nr) of the dense view in place (the full data, or a batch view inside a BatchScope) to
+// the host: A column-major with leading dimension lda_out, y with nr rows (x nout, column-major)
+static void read_rows(scs_ctx* c, int64_t r0, int64_t nr, double* A, int64_t lda_out, double* y) {
+  if (A && nr > 0) {
+    double* C = dalloc<double>(c, (size_t)c->Npad * 128);
+    for (int64_t p = 0; p < c->dcp / 128; ++p) {
+      const int64_t j0 = p * 128, nc = std::min<int64_t>(128, c->dc - j0);
+      if (nc <= 0) break;
+      HCK(launch_retile(C, 0, c->A, c->a32, c->Npad, p, 0, c->st));   // fp32-stored rows come back widened
+      HCK(hipMemcpy2DAsync(A + j0 * lda_out, sizeof(double) * lda_out, C + r0, sizeof(double) * c->Npad,
+                           sizeof(double) * nr, nc, hipMemcpyDeviceToHost, c->st));
+    }
+    sync(c);
+    dfree_t(c, C);
+  }
+  if (y && nr > 0 && multi(c))   // nr x nout, column-major with leading dimension nr
+    HCK(hipMemcpy2DAsync(y, sizeof(double) * nr, c->y + r0, sizeof(double) * c->Npad, sizeof(double) * nr, c->nout,
+                         hipMemcpyDeviceToHost, c->st));
+  else if (y && nr > 0)
+    d2h(c, y, c->y + r0, nr);
+  sync(c);
+}
+
 int scs_get_data(scs_ctx* c, int64_t r0, int64_t nr, double* A, int64_t lda_out, double* y) {
   if (is_group(c)) return group_get_data(c, r0, nr, A, lda_out, y);
   return guarded(c, [&] {
     if (!c->has_data || c->generic) fail(c, SCS_ERR_STATE, "no data");
     if (c->sparse && A) fail(c, SCS_ERR_ARG, "sparse A: use scs_get_sparse");
     if (r0 < 0 || nr < 0 || r0 + nr > c->N) fail(c, SCS_ERR_ARG, "row range out of bounds");
-    if (A && nr > 0) {
-      double* C = dalloc<double>(c, (size_t)c->Npad * 128);
-      for (int64_t p = 0; p < c->dcp / 128; ++p) {
-        const int64_t j0 = p * 128, nc = std::min<int64_t>(128, c->dc - j0);
-        if (nc <= 0) break;
-        HCK(launch_retile(C, 0, c->A, c->a32, c->Npad, p, 0, c->st));   // fp32-stored rows come back widened
-        HCK(hipMemcpy2DAsync(A + j0 * lda_out, sizeof(double) * lda_out, C + r0, sizeof(double) * c->Npad,
-                             sizeof(double) * nr, nc, hipMemcpyDeviceToHost, c->st));
-      }
-      sync(c);
-      dfree_t(c, C);
-    }
-    if (y && nr > 0 && multi(c))   // nr x nout, column-major with leading dimension nr
-      HCK(hipMemcpy2DAsync(y, sizeof(double) * nr, c->y + r0, sizeof(double) * c->Npad, sizeof(double) * nr, c->nout,
-                           hipMemcpyDeviceToHost, c->st));
-    else if (y && nr > 0)
-      d2h(c, y, c->y + r0, nr);
-    sync(c);
+    read_rows(c, r0, nr, A, lda_out, y);
   });
 }
 
@@ -4797,10 +4830,15 @@ int scs_set_batches(scs_ctx* c, const int64_t* rows, const int64_t* offsets, int
     clear_batches(c);
     invalidate_caches(c);
     if (nbatch == 0) return;
-    if (multi(c))
+    if (multi(c) && !c->multi_batches)
       fail(c, SCS_ERR_ARG, "scs_set_batches: minibatches (batch_size / slice_samples) are not supported with "
-                           "scs_set_outputs (nout = %d)", c->nout);
+                           "scs_set_outputs (nout = %d) unless multi_batches / scs_set_multi_batches is on", c->nout);
     if (!c->has_data) fail(c, SCS_ERR_STATE, "no data: call scs_set_data / scs_gen_data first");
+    if (multi(c) && c->sparse)
+      fail(c, SCS_ERR_ARG, "scs_set_batches: minibatches with scs_set_outputs (nout = %d) need a dense A (a sparse A, "
+                           "scs_set_sparse_outputs included, is not supported with multi_batches / "
+                           "scs_set_multi_batches)", c->nout);
+    if (multi(c)) c->mb_gather = multi_gather_arm(c->a32);
     if (c->generic) fail(c, SCS_ERR_ARG, "a ProblemGeneric has no samples to batch");
     if (nbatch < 0 || !rows || !offsets || offsets[0] != 0) fail(c, SCS_ERR_ARG, "scs_set_batches: bad batch list");
     for (int64_t b = 0; b < nbatch; ++b)
@@ -5821,12 +5859,79 @@ int scs_set_multi_sample(scs_ctx* c, int on) {
     const int v = on ? 1 : 0;
     if (v == c->multi_sample) return;
     c->multi_sample = v;
-    if (!v && multi(c) && c->has_data && !c->sparse && c->At) {
+    if (!v && multi(c) && c->has_data && !c->sparse) {   // the view in place and every pooled batch view
       HCK(hipSetDevice(c->dev));
       sync(c);
-      free_buffers(c, *c, VB_SAMPLE);
-      c->nstiles = 0;
+      auto give_back = [c](ViewData& w) {
+        if (!w.At) return;
+        free_buffers(c, w, VB_SAMPLE);
+        static_cast<ViewSample&>(w) = ViewSample();
+      };
+      give_back(*c);
+      for (NView& w : c->bpool) give_back(w);
     }
+  });
+}
+
+// Minibatches with nout set (a dense A): stored without effect while nout is unset.  Changing it drops
+// the pooled batch views; switching it off with a list registered on a multi-output context clears the list.
+int scs_set_multi_batches(scs_ctx* c, int on) {
+  if (!c) return SCS_ERR_ARG;
+  if (is_group(c)) {
+    c->err = "scs_set_multi_batches takes a single-device context (scs_create): a multi-device context "
+             "(devices=[...]) is not supported with nout";
+    return SCS_ERR_ARG;
+  }
+  return guarded(c, [&] {
+    const int v = on ? 1 : 0;
+    if (v == c->multi_batches) return;
+    HCK(hipSetDevice(c->dev));
+    sync(c);
+    c->multi_batches = v;
+    if (!v && multi(c) && !c->boff.empty()) {
+      clear_batches(c);
+    } else {
+      free_dense_views(c);   // the pooled views go, the registered list stays
+      free_sparse_views(c);
+      if (c->bsel >= 0) select_batch(c, c->bsel);
+    }
+    invalidate_caches(c);
+    sync(c);
+  });
+}
+
+// Batch b of the registered list as scs_select_batch gathers it: its n_b x d rows widened to fp64
+// (column-major, leading dimension lda) and its n_b (x nout) targets.  The selection is left as found.
+int scs_get_batch_data(scs_ctx* c, int64_t b, double* A_out, int64_t lda, double* Y_out) {
+  if (!c) return SCS_ERR_ARG;
+  if (is_group(c)) {
+    c->err = "scs_get_batch_data takes a single-device context (scs_create)";
+    return SCS_ERR_ARG;
+  }
+  return guarded(c, [&] {
+    const int64_t nb = c->boff.empty() ? 0 : (int64_t)c->boff.size() - 1;
+    if (b < 0 || b >= nb) fail(c, SCS_ERR_ARG, "scs_get_batch_data: batch %lld of %lld", (long long)b, (long long)nb);
+    const int64_t n = c->boff[b + 1] - c->boff[b];
+    if (A_out && lda < n) fail(c, SCS_ERR_ARG, "scs_get_batch_data: lda %lld < n_b %lld", (long long)lda, (long long)n);
+    HCK(hipSetDevice(c->dev));
+    const int64_t was = c->bsel;
+    struct Restore {   // the caller's selection comes back even when the read fails
+      scs_ctx* c;
+      int64_t was;
+      ~Restore() {
+        try {
+          select_batch(c, was);
+          (void)hipStreamSynchronize(c->st);
+        } catch (...) {
+          unselect_view(c);
+          c->bsel = -1;
+        }
+      }
+    } restore{c, was};
+    select_batch(c, b);
+    if (c->spview >= 0) fail(c, SCS_ERR_ARG, "scs_get_batch_data: batch %lld is held as a sparse view", (long long)b);
+    BatchScope bs(c);
+    read_rows(c, 0, c->N, A_out, lda, Y_out);
   });
 }
 

@@ -16,7 +16,7 @@ import SelfConcordantSmoothOptimization: step!, init!, ProximalMethod, ProxModel
 
 export DeviceProblem, configure!, iterate_device!, set_gram_cache!, set_solver!, rccl_unique_id, set_comm_rccl!,
        set_comm_callback!, set_test!, set_test_device!, set_compute_f32!, fallback_counts, data_info, samplewise,
-       set_sparse_batches!, set_sparse_sample!, batch_info, set_multi_sample!,
+       set_sparse_batches!, set_sparse_sample!, batch_info, set_multi_sample!, set_multi_batches!,
        multi_sample_system
 
 const lib = joinpath(@__DIR__, "..", "scsopt", "libscsopt.so")
@@ -255,17 +255,20 @@ end
 # count d; A stays on the device as one N x d block (Matrix{Float32}: stored as fp32).  One device, one
 # rank, the full batch; an Atest takes an Ntest x K ytest.  multi_sample = true: with N*K + 1 <= d*K
 # ProxGGNSCORE runs the reference's sample-space branch on the device instead of being refused
-# (scs_set_multi_sample).
+# (scs_set_multi_sample).  multi_batches = true: iterate_device!(...; batch_size) / set_batches! are accepted
+# (a dense A; the batch's rows of A and Y are gathered on the device) instead of being refused
+# (scs_set_multi_batches).
 function DeviceProblem(A::Union{Matrix{Float64},Matrix{Float32}}, Y::AbstractMatrix, x0::Vector{Float64},
                        loss::Symbol, λ; out_fn::Union{Symbol,Nothing}=nothing, scale::Float64=1.0 / size(A, 1),
                        L=nothing, sol::Vector{Float64}=zero(x0), C_set=nothing, P=nothing, device::Integer=0,
-                       Atest=nothing, ytest=nothing, multi_sample::Bool=false)
+                       Atest=nothing, ytest=nothing, multi_sample::Bool=false, multi_batches::Bool=false)
     N, d = size(A)
     K = size(Y, 2)
     (size(Y, 1) == N && length(x0) == d * K) ||
         throw(DimensionMismatch("Y must be N x K and length(x0) = size(A, 2) * K"))
     ctx = create_ctx(device)
     multi_sample && chk(ccall((:scs_set_multi_sample, lib), Cint, (Ptr{Cvoid}, Cint), ctx, 1), ctx)
+    multi_batches && chk(ccall((:scs_set_multi_batches, lib), Cint, (Ptr{Cvoid}, Cint), ctx, 1), ctx)
     chk(ccall((:scs_set_outputs, lib), Cint, (Ptr{Cvoid}, Cint), ctx, K), ctx)
     Ym = Matrix{Float64}(Y)
     if A isa Matrix{Float32}
@@ -312,6 +315,13 @@ end
 # (scs_set_multi_sample; off by default: that shape is refused).  Stored without effect without nout.
 function set_multi_sample!(model::DeviceProblem, on::Bool=true)
     chk(ccall((:scs_set_multi_sample, lib), Cint, (Ptr{Cvoid}, Cint), model.ctx, on ? 1 : 0), model.ctx)
+    return model
+end
+
+# Minibatches of a multi-output problem (a dense A) on or off (scs_set_multi_batches; off by default:
+# set_batches! is refused).  Stored without effect without nout; switching it off clears a registered list.
+function set_multi_batches!(model::DeviceProblem, on::Bool=true)
+    chk(ccall((:scs_set_multi_batches, lib), Cint, (Ptr{Cvoid}, Cint), model.ctx, on ? 1 : 0), model.ctx)
     return model
 end
 

@@ -116,6 +116,7 @@ _SIGS = {
     "scs_set_outputs": (C.c_int, [C.c_void_p, C.c_int]),
     "scs_set_sparse_outputs": (C.c_int, [C.c_void_p, C.c_int]),
     "scs_set_multi_sample": (C.c_int, [C.c_void_p, C.c_int]),
+    "scs_set_multi_batches": (C.c_int, [C.c_void_p, C.c_int]),
     "scs_get_outputs": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), c_i64p]),
     "scs_set_data": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, c_dp, C.c_int64, c_dp, C.c_int64, C.c_int64]),
     "scs_gen_data": (C.c_int, [C.c_void_p, C.POINTER(Synth)]),
@@ -166,6 +167,7 @@ _SIGS = {
     "scs_set_group_map": (C.c_int, [C.c_void_p, c_i64p, C.c_int64]),
     "scs_set_batches": (C.c_int, [C.c_void_p, c_i64p, c_i64p, C.c_int64]),
     "scs_select_batch": (C.c_int, [C.c_void_p, C.c_int64]),
+    "scs_get_batch_data": (C.c_int, [C.c_void_p, C.c_int64, c_dp, C.c_int64, c_dp]),
     "scs_set_sparse_batches": (C.c_int, [C.c_void_p, C.c_int]),
     "scs_set_sparse_sample": (C.c_int, [C.c_void_p, C.c_int]),
     "scs_batch_info": (C.c_int, [C.c_void_p, c_i64p, c_i64p, c_i64p]),

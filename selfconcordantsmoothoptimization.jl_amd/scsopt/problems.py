@@ -97,7 +97,7 @@ class Problem:
                  out_fn: Optional[OutFn] = None, name=None, device=0, comm=None, N_global=None, row0=0,
                  sparse_f32=False, devices=None, device_exchange="rccl", Ntest_global=None, test_row0=0,
                  dense_f32=False, sparse_batches=False, sparse_sample=False, sparse_outputs=False, multi_sample=False,
-                 _ctx=None):
+                 multi_batches=False, _ctx=None):
         if len(args) == 5:
             A, y, x0, f, lam = args
         elif len(args) == 3:
@@ -132,6 +132,14 @@ class Problem:
         if self.multi_sample and devices is not None:
             raise ValueError("multi_sample=True takes a single-device context: devices=[...] is not supported with "
                              "nout")
+        # multi_batches: with nout set, minibatches (batch_size / slice_samples / set_batches) of a dense A are
+        # gathered on the device instead of being refused (scs_set_multi_batches)
+        if not isinstance(multi_batches, (bool, np.bool_)):
+            raise TypeError(f"multi_batches must be a bool, got {type(multi_batches).__name__}")
+        self.multi_batches = bool(multi_batches)
+        if self.multi_batches and devices is not None:
+            raise ValueError("multi_batches=True takes a single-device context: devices=[...] is not supported with "
+                             "nout")
         self.nout = self._check_outputs(f, out_fn, A, comm, devices, _ctx)
         self.d = self.m // self.nout   # A's columns
         if f.kind == "callback":   # the data stays with the caller's closures; the device holds none
@@ -160,6 +168,8 @@ class Problem:
             self.ctx.check(_lib.lib.scs_set_sparse_outputs(self.ctx.h, 1))
         if self.multi_sample:     # likewise inert without nout
             self.ctx.check(_lib.lib.scs_set_multi_sample(self.ctx.h, 1))
+        if self.multi_batches:    # likewise
+            self.ctx.check(_lib.lib.scs_set_multi_batches(self.ctx.h, 1))
         if self.nout > 1:   # before the data door: its m is then A's column count d, y is N x nout
             self.ctx.check(_lib.lib.scs_set_outputs(self.ctx.h, self.nout))
         if comm is not None and comm.active and _ctx is None:
@@ -866,6 +876,31 @@ class Problem:
         shape is refused.  Stored without effect while nout is unset.  scs_set_multi_sample."""
         self.ctx.check(_lib.lib.scs_set_multi_sample(self.ctx.h, int(bool(on))))
         self.multi_sample = bool(on)
+
+    def set_multi_batches(self, on=True):
+        """Opt-in: with nout set, set_batches / iterate(batch_size=..., slice_samples=...) accept a dense A: a
+        batch's rows of A and of Y are gathered on the device in one launch, and ProxGGNSCORE picks its branch per
+        batch (the sample-space one needs multi_sample).  Off: refused.  Stored without effect while nout is
+        unset; changing it drops the pooled views, and switching it off clears a multi-output problem's
+        registered list.  scs_set_multi_batches."""
+        self.ctx.check(_lib.lib.scs_set_multi_batches(self.ctx.h, int(bool(on))))
+        self.multi_batches = bool(on)
+        if not self.multi_batches and self.nout > 1:
+            self._bsel, self._bsizes = -1, []
+
+    def get_batch_data(self, b):
+        """(A_b, y_b) of registered batch b as a step sees it, gathered by select_batch's own path: the n_b x d
+        rows as float64 and the n_b (x nout) targets.  The selection stays as it was.  scs_get_batch_data."""
+        b = int(b)
+        sizes = getattr(self, "_bsizes", [])
+        if not 0 <= b < len(sizes):
+            raise IndexError(f"batch {b} of {len(sizes)}")
+        n = sizes[b]
+        Ab = np.zeros((n, self.d), order="F")
+        yb = np.zeros((n, self.nout), order="F") if self.nout > 1 else np.zeros(n)
+        self.ctx.check(_lib.lib.scs_get_batch_data(self.ctx.h, b, C.cast(Ab.ctypes.data, _lib.c_dp), n,
+                                                   C.cast(yb.ctypes.data, _lib.c_dp)))
+        return Ab, yb
 
     def batch_info(self):
         """(sparse batch views held, their device bytes, views built since set_batches) -- scs_batch_info."""
