@@ -317,6 +317,25 @@ int scs_set_multi_sample(scs_ctx* ctx, int on);
  * off with a list registered on a multi-output context clears the list.  Refused on multi-device
  * contexts as scs_set_outputs is.                                                                  */
 int scs_set_multi_batches(scs_ctx* ctx, int on);
+/* Minibatches with nout set on a sparse A (off by default).  With on != 0 -- and scs_set_multi_batches
+ * on, which stays the gate -- scs_set_batches also accepts a multi-output context whose sparse A came
+ * through scs_set_sparse / scs_set_sparse_device in the scs_set_sparse_outputs mode (fp64 or fp32
+ * values).  By default a batch is a densified view, the reference's (Matrix(As'), Matrix(ys')): its
+ * rows of the d-column CSR written into a dense n_b x d block and Y_b gathered, after which a step
+ * runs the dense multi-output path (all three methods; ProxGGNSCORE picks its branch per batch as
+ * under scs_set_multi_batches) and equals the step of a dense context holding A[rows_b], Y[rows_b].
+ * With scs_set_sparse_batches also on, ProxLQNSCORE's batches are sparse K-column views instead: the
+ * blocked copies scs_set_sparse would build from A[rows_b], Y[rows_b] in the scs_set_sparse_outputs
+ * mode, kept and refilled under scs_set_sparse_batches' budget rules; scs_set_sparse_sample stays
+ * without effect.  On those views the one-pass K-column kernel runs with 256 rows per workgroup
+ * where that measured faster (nout > 4) and with 1024 otherwise; SCS_MULTI_SPARSE_NARROW=0 / 1 (read
+ * at scs_set_batches) forces 1024 / 256: the same bits.
+ * scs_multi_products_eval on a context with a selected sparse view runs on that view (V is n_b x K);
+ * scs_get_batch_data returns the batch's rows densified, and Y_b; scs_batch_info counts both kinds
+ * of view.  Stored without effect while nout is unset or on a dense A; changing it drops the pooled
+ * batch views, and switching it off with a list registered on a sparse multi-output context clears
+ * the list.  Refused on multi-device contexts as scs_set_outputs is.                              */
+int scs_set_multi_sparse_batches(scs_ctx* ctx, int on);
 
 /* ---- data  (Problem(A, y, ...) -- problems.jl:61-81) --------------------- */
 /* Upload host A (column-major, N x m, leading dim lda) and y (N).  N is the

@@ -27,6 +27,9 @@ struct SpBlkT {
   // (scs_set_sparse_outputs, multi_sparse.hip) cuts each 16384-index block into kp sub-blocks and the
   // products still write one partial per group of kp
   int kp = 1;
+  // the K-column product's workgroup form on this copy: 0 1024 rows per workgroup, 1 256 (set where a
+  // sparse batch view is built, scs_set_multi_sparse_batches; the full data and held-out sets keep 0)
+  int narrow = 0;
   int64_t nnz = 0;   // entries of the copy
   int64_t* ptr = nullptr;
   uint16_t* lidx = nullptr;

@@ -479,10 +479,13 @@ int multi_spmm_group(int K);
 int multi_spmm_default(int K, int f32);
 hipError_t launch_multi_spmm_pack(const double* src, int64_t ld, int64_t nvalid, int64_t ntotal, int K, double* dst,
                                   hipStream_t st);
-const char* multi_spmm_kernel_name(int f32, int K);
+// narrow: the 256-row workgroup form (a sparse batch view's SpBlkT::narrow; the same bits as the 1024-row
+// form); multi_spmm_narrow_default: whether a view of K columns takes it when nothing forces a form
+int multi_spmm_narrow_default(int K, int f32);
+const char* multi_spmm_kernel_name(int f32, int K, int narrow = 0);
 hipError_t launch_multi_spmm(const int64_t* ptr, const uint16_t* lidx, const void* val, int f32, const double* Xt,
                              int K, int64_t nrows, int64_t ncols, int shift, double* out, int64_t ldo,
-                             hipStream_t st);
+                             hipStream_t st, int narrow = 0);
 
 // ---- sparse.hip (LDS-blocked gathers; out[b*ldo + r] = Σ_{p in row r, block b} val[p] x[(b<<shift) + lidx[p]])
 int spmv_blk_shift(int64_t ncols);

@@ -14,8 +14,10 @@
 // layout -- and the kernel writes one partial per (group, column): out[(g·K + l)·ldo + r].  The
 // partial counts are the single-vector layout's.
 //
-// Kernel: a workgroup owns (1024 consecutive rows, one group); lane = one row with KP register
-// accumulators.  Per sub-block of the group: the slice's loads from the packed operand (in parts of
+// Kernel: a workgroup owns (ROWS consecutive rows, one group), ROWS = 1024 or 256 threads; lane = one
+// row with KP register accumulators.  (The 256-row form is the batch-shaped geometry of DESIGN §2l: four
+// times the workgroups on a view of few rows, four times the staged elements per thread; the LDS layout
+// and every (row, column) sum are the 1024-row form's, so both write the same bits.)  Per sub-block of the group: the slice's loads from the packed operand (in parts of
 // 8 or 4 per thread, a part's loads all in flight), barrier, the LDS stores, barrier, then each lane
 // streams its row's slots of that sub-block (one slot's loads in flight ahead of the compute; the
 // row's slot range and first slot of the NEXT sub-block are requested before the staging / under the
@@ -37,7 +39,8 @@
 
 namespace scs {
 
-constexpr int MSP_THREADS = 1024;        // = rows per workgroup
+constexpr int MSP_THREADS = 1024;        // = rows per workgroup (the wide form: full data, held-out sets)
+constexpr int MSP_NARROW = 256;          // ... of the narrow form (sparse batch views only, SpBlkT::narrow)
 constexpr int MSP_LDS_IDX = 1 << 14;     // W·KP: the slice without its zero row
 constexpr int MSP_PADIDX = 1 << 14;      // build_blocked's padding index (spmv_pad_index())
 
@@ -73,26 +76,29 @@ __device__ __forceinline__ void msp_load(MspSlot<float, 8>& w, const uint16_t* _
   }
 }
 
-template <typename VT, int SLOT, int KP>
-__global__ __launch_bounds__(MSP_THREADS) void multi_spmm_blk_kernel(const int64_t* __restrict__ ptr,
-                                                                     const uint16_t* __restrict__ lidx,
-                                                                     const VT* __restrict__ val,
-                                                                     const double* __restrict__ Xt, int K,
-                                                                     /* Xt: ncols x KP, zero beyond column K */
-                                                                     int64_t nrows, int64_t ncols, int shift,
-                                                                     int nsub, double* __restrict__ out,
-                                                                     int64_t ldo) {
+// the body of both forms: ROWS = the workgroup's threads = its rows
+template <typename VT, int SLOT, int KP, int ROWS>
+__device__ __forceinline__ void multi_spmm_blk_body(const int64_t* __restrict__ ptr, const uint16_t* __restrict__ lidx,
+                                                    const VT* __restrict__ val, const double* __restrict__ Xt, int K,
+                                                    /* Xt: ncols x KP, zero beyond column K */
+                                                    int64_t nrows, int64_t ncols, int shift, int nsub,
+                                                    double* __restrict__ out, int64_t ldo) {
   constexpr int SH = SLOT == 4 ? 2 : 3;
   constexpr int LK = KP == 2 ? 1 : KP == 4 ? 2 : KP == 8 ? 3 : 4;
   static_assert((1 << LK) == KP, "KP is 2, 4, 8 or 16");
-  constexpr int NH = KP == 16 ? 4 : 2;                  // the slice is staged in NH parts (registers: 16 accumulators)
+  static_assert(ROWS == MSP_THREADS || ROWS == MSP_NARROW, "1024 or 256 rows per workgroup");
+  // the slice is staged in NR rounds of NH parts of PER elements per thread (registers: 16 accumulators
+  // beside a part); the narrow form keeps NH and PER and takes four rounds (a rolled loop: unrolled, the
+  // 4·NH·PER bounds masks of a sub-block do not fit the scalar registers)
+  constexpr int NR = MSP_THREADS / ROWS;
+  constexpr int NH = KP == 16 ? 4 : 2;
   constexpr int PER = MSP_LDS_IDX / MSP_THREADS / NH;   // staged elements per thread and part
   constexpr int CH = KP / 2;   // 16-byte chunks of a slice row
   __shared__ __attribute__((aligned(256))) double xs[MSP_LDS_IDX + KP];
   const int W = 1 << shift;              // W·KP <= MSP_LDS_IDX (launch_multi_spmm checks)
   const int nslice = W << LK;            // the slice; its zero row follows
   const int g = blockIdx.y;
-  const int64_t r = (int64_t)blockIdx.x * MSP_THREADS + threadIdx.x;
+  const int64_t r = (int64_t)blockIdx.x * ROWS + threadIdx.x;
   const bool live = r < nrows;
   double acc[KP];
 #pragma unroll
@@ -124,18 +130,22 @@ __global__ __launch_bounds__(MSP_THREADS) void multi_spmm_blk_kernel(const int64
     const double* src = Xt + (c0 << LK);
     // stage the slice in NH parts: a part's loads of a thread all in flight before its LDS stores
     double t[PER];
+#pragma unroll 1
+    for (int rd = 0; rd < NR; ++rd) {
+      const int i0 = threadIdx.x + rd * (NH * PER * ROWS);
 #pragma unroll
-    for (int h = 0; h < NH; ++h) {
+      for (int h = 0; h < NH; ++h) {
 #pragma unroll
-      for (int k = 0; k < PER; ++k) {
-        const int i = threadIdx.x + (h * PER + k) * MSP_THREADS;
-        t[k] = (i < nval) ? src[i] : 0.0;
-      }
-      if (h == 0) __syncthreads();   // the previous sub-block's gathers are done
+        for (int k = 0; k < PER; ++k) {
+          const int i = i0 + (h * PER + k) * ROWS;
+          t[k] = (i < nval) ? src[i] : 0.0;
+        }
+        if (h == 0 && rd == 0) __syncthreads();   // the previous sub-block's gathers are done
 #pragma unroll
-      for (int k = 0; k < PER; ++k) {
-        const int i = threadIdx.x + (h * PER + k) * MSP_THREADS;
-        if (i < nslice) xs[i ^ (((i >> 5) & (CH - 1)) << 1)] = t[k];   // the row's chunks swizzled (below)
+        for (int k = 0; k < PER; ++k) {
+          const int i = i0 + (h * PER + k) * ROWS;
+          if (i < nslice) xs[i ^ (((i >> 5) & (CH - 1)) << 1)] = t[k];   // the row's chunks swizzled (below)
+        }
       }
     }
     if (threadIdx.x < KP) xs[nslice + threadIdx.x] = 0.0;
@@ -174,6 +184,29 @@ __global__ __launch_bounds__(MSP_THREADS) void multi_spmm_blk_kernel(const int64
   }
 }
 
+// the 1024-row form (its name and launch bounds as before the body took ROWS) and the 256-row form
+template <typename VT, int SLOT, int KP>
+__global__ __launch_bounds__(MSP_THREADS) void multi_spmm_blk_kernel(const int64_t* __restrict__ ptr,
+                                                                     const uint16_t* __restrict__ lidx,
+                                                                     const VT* __restrict__ val,
+                                                                     const double* __restrict__ Xt, int K,
+                                                                     int64_t nrows, int64_t ncols, int shift,
+                                                                     int nsub, double* __restrict__ out,
+                                                                     int64_t ldo) {
+  multi_spmm_blk_body<VT, SLOT, KP, MSP_THREADS>(ptr, lidx, val, Xt, K, nrows, ncols, shift, nsub, out, ldo);
+}
+
+template <typename VT, int SLOT, int KP>
+__global__ __launch_bounds__(MSP_NARROW) void multi_spmm_blk256_kernel(const int64_t* __restrict__ ptr,
+                                                                       const uint16_t* __restrict__ lidx,
+                                                                       const VT* __restrict__ val,
+                                                                       const double* __restrict__ Xt, int K,
+                                                                       int64_t nrows, int64_t ncols, int shift,
+                                                                       int nsub, double* __restrict__ out,
+                                                                       int64_t ldo) {
+  multi_spmm_blk_body<VT, SLOT, KP, MSP_NARROW>(ptr, lidx, val, Xt, K, nrows, ncols, shift, nsub, out, ldo);
+}
+
 // The packed operand of the kernel above: dst[j*KP + l] = src[j + ld*l] for j < nvalid and l < K, else 0
 // (j < ntotal).  x = vec(X): ld = nvalid = d, ntotal = d_pad; an N x K operand V: ld = nvalid = ntotal = N_pad.
 __global__ void multi_spmm_pack_kernel(const double* __restrict__ src, int64_t ld, int64_t nvalid, int64_t ntotal,
@@ -204,24 +237,44 @@ int multi_spmm_default(int K, int f32) {
   return K >= 3;
 }
 
-const char* multi_spmm_kernel_name(int f32, int K) {
-  static const char* const names[2][4] = {
-      {"multi_spmm_blk_kernel<double, 4, 2>", "multi_spmm_blk_kernel<double, 4, 4>",
-       "multi_spmm_blk_kernel<double, 4, 8>", "multi_spmm_blk_kernel<double, 4, 16>"},
-      {"multi_spmm_blk_kernel<float, 8, 2>", "multi_spmm_blk_kernel<float, 8, 4>",
-       "multi_spmm_blk_kernel<float, 8, 8>", "multi_spmm_blk_kernel<float, 8, 16>"}};
-  const int kp = msp_kp(K);
-  return names[f32 ? 1 : 0][kp == 2 ? 0 : kp == 4 ? 1 : kp == 8 ? 2 : 3];
+// The narrow form on sparse batch views (its one place).  The rule of §2i / §2k: a form is the default for
+// a (KP, storage) only where its whole range over alternated rounds lies below the other's.  Measured on
+// 2^14-row views of N = 2^20, d = 2^16, 655 nonzeros per row (profiles/multi_sparse_batches/),
+// a step's four products: KP = 8 fp64 0.435 (0.428 .. 0.459) against 0.697 (0.686 .. 0.713) ms, fp32 0.373
+// (0.367 .. 0.381) against 0.440 (0.432 .. 0.460); KP = 16 fp64 0.819 (0.813 .. 0.830) against 0.912
+// (0.906 .. 0.924), fp32 0.859 (0.852 .. 0.873) against 0.974 (0.963 .. 0.978).  KP = 2 and 4 were not
+// measured and keep 1024 rows (SCS_MULTI_SPARSE_NARROW=1 selects the narrow form there).
+int multi_spmm_narrow_default(int K, int f32) {
+  (void)f32;
+  return msp_kp(K) >= 8;
 }
 
-template <typename VT, int SLOT>
+const char* multi_spmm_kernel_name(int f32, int K, int narrow) {
+  static const char* const names[2][2][4] = {
+      {{"multi_spmm_blk_kernel<double, 4, 2>", "multi_spmm_blk_kernel<double, 4, 4>",
+        "multi_spmm_blk_kernel<double, 4, 8>", "multi_spmm_blk_kernel<double, 4, 16>"},
+       {"multi_spmm_blk_kernel<float, 8, 2>", "multi_spmm_blk_kernel<float, 8, 4>",
+        "multi_spmm_blk_kernel<float, 8, 8>", "multi_spmm_blk_kernel<float, 8, 16>"}},
+      {{"multi_spmm_blk256_kernel<double, 4, 2>", "multi_spmm_blk256_kernel<double, 4, 4>",
+        "multi_spmm_blk256_kernel<double, 4, 8>", "multi_spmm_blk256_kernel<double, 4, 16>"},
+       {"multi_spmm_blk256_kernel<float, 8, 2>", "multi_spmm_blk256_kernel<float, 8, 4>",
+        "multi_spmm_blk256_kernel<float, 8, 8>", "multi_spmm_blk256_kernel<float, 8, 16>"}}};
+  const int kp = msp_kp(K);
+  return names[narrow ? 1 : 0][f32 ? 1 : 0][kp == 2 ? 0 : kp == 4 ? 1 : kp == 8 ? 2 : 3];
+}
+
+template <typename VT, int SLOT, bool NARROW>
 static void msp_dispatch(int kp, dim3 grid, hipStream_t st, const int64_t* ptr, const uint16_t* lidx, const VT* val,
                          const double* Xt, int K, int64_t nrows, int64_t ncols, int shift, int nsub, double* out,
                          int64_t ldo) {
 #define SCS_MSP_CASE(KP)                                                                                             \
   case KP:                                                                                                           \
-    hipLaunchKernelGGL((multi_spmm_blk_kernel<VT, SLOT, KP>), grid, dim3(MSP_THREADS), 0, st, ptr, lidx, val, Xt, K,  \
-                       nrows, ncols, shift, nsub, out, ldo);                                                         \
+    if (NARROW)                                                                                                      \
+      hipLaunchKernelGGL((multi_spmm_blk256_kernel<VT, SLOT, KP>), grid, dim3(MSP_NARROW), 0, st, ptr, lidx, val, Xt, \
+                         K, nrows, ncols, shift, nsub, out, ldo);                                                    \
+    else                                                                                                             \
+      hipLaunchKernelGGL((multi_spmm_blk_kernel<VT, SLOT, KP>), grid, dim3(MSP_THREADS), 0, st, ptr, lidx, val, Xt,   \
+                         K, nrows, ncols, shift, nsub, out, ldo);                                                    \
     break;
   switch (kp) { SCS_MSP_CASE(2) SCS_MSP_CASE(4) SCS_MSP_CASE(8) SCS_MSP_CASE(16) }
 #undef SCS_MSP_CASE
@@ -240,17 +293,25 @@ hipError_t launch_multi_spmm_pack(const double* src, int64_t ld, int64_t nvalid,
 
 hipError_t launch_multi_spmm(const int64_t* ptr, const uint16_t* lidx, const void* val, int f32, const double* Xt,
                              int K, int64_t nrows, int64_t ncols, int shift, double* out, int64_t ldo,
-                             hipStream_t st) {
+                             hipStream_t st, int narrow) {
   if (K < 2 || K > 16) return hipErrorInvalidValue;
   if (nrows <= 0 || ncols <= 0) return hipSuccess;   // no rows, or nothing to gather from
   const int kp = msp_kp(K);
   if (shift < 0 || ((int64_t)kp << shift) > MSP_LDS_IDX || spmv_pad_index() != MSP_PADIDX) return hipErrorInvalidValue;
   const int nsub = (int)ceil_div(ncols, (int64_t)1 << shift);
-  const dim3 grid((unsigned)ceil_div(nrows, MSP_THREADS), (unsigned)ceil_div(nsub, kp));
-  if (f32)
-    msp_dispatch<float, 8>(kp, grid, st, ptr, lidx, (const float*)val, Xt, K, nrows, ncols, shift, nsub, out, ldo);
+  const dim3 grid((unsigned)ceil_div(nrows, narrow ? MSP_NARROW : MSP_THREADS), (unsigned)ceil_div(nsub, kp));
+  if (f32 && narrow)
+    msp_dispatch<float, 8, true>(kp, grid, st, ptr, lidx, (const float*)val, Xt, K, nrows, ncols, shift, nsub, out,
+                                       ldo);
+  else if (f32)
+    msp_dispatch<float, 8, false>(kp, grid, st, ptr, lidx, (const float*)val, Xt, K, nrows, ncols, shift, nsub, out,
+                                        ldo);
+  else if (narrow)
+    msp_dispatch<double, 4, true>(kp, grid, st, ptr, lidx, (const double*)val, Xt, K, nrows, ncols, shift, nsub,
+                                        out, ldo);
   else
-    msp_dispatch<double, 4>(kp, grid, st, ptr, lidx, (const double*)val, Xt, K, nrows, ncols, shift, nsub, out, ldo);
+    msp_dispatch<double, 4, false>(kp, grid, st, ptr, lidx, (const double*)val, Xt, K, nrows, ncols, shift, nsub,
+                                         out, ldo);
   return hipGetLastError();
 }
 

@@ -105,6 +105,14 @@ struct scs_ctx : ViewData {
   // launch_gather_y per further target column
   int multi_batches = 0;
   int mb_gather = 1;
+  // scs_set_multi_sparse_batches: with nout and multi_batches set, scs_set_batches also accepts a sparse A
+  // held in the scs_set_sparse_outputs mode (stored without effect while nout is unset or on a dense A).
+  // Its batches are densified views (bpool: the d-column rows through launch_densify_rows, Y_b gathered)
+  // or, under ProxLQNSCORE with scs_set_sparse_batches, sparse K-column views (spool).  msb_narrow: the
+  // workgroup form of the one-pass kernel on those sparse views, read where the list is registered
+  // (multi_narrow_form)
+  int multi_sparse_batches = 0;
+  int msb_narrow = 0;
   double* mXt = nullptr;   // x = vec(X) repacked K-contiguous (dcp x K, zero beyond dc): launch_multi_pack_x
   double* mVt = nullptr;   // an N x K operand of Aᵀ V repacked K-contiguous (grow-only, mVt_cap doubles)
   int64_t mVt_cap = 0;
@@ -973,9 +981,12 @@ void free_sample_sys(scs_ctx* c) {
 
 // 0: dense batch views, 1: sparse views for ProxLQNSCORE, 2: sparse views for ProxGGNSCORE's batches
 // with n_b + 1 <= m (dense ones for the rest) -- one rank only: the sharded sample branch needs a dense A
+// A multi-output context (scs_set_multi_sparse_batches): 1 for ProxLQNSCORE (sparse K-column views), else
+// 0 (densified views); never 2 -- scs_set_sparse_sample stays without effect there.
 int batch_view_kind(const scs_ctx* c, int method) {
   if (!c->sparse_batches || !c->sparse) return 0;
   if (method == SCS_PROX_LQNSCORE) return 1;
+  if (multi(c)) return 0;
   if (method == SCS_PROX_GGNSCORE && c->sparse_sample && !sharded(c)) return 2;
   return 0;
 }
@@ -1115,11 +1126,17 @@ T* bscratch(scs_ctx* c, int k, size_t n) {
 // ssv (ProxGGNSCORE's sample space, scs_set_sparse_sample): the view also keeps the gathered CSR rows and
 // the Gram-blocked copy of its CSC -- colptr_b / rowidx_s / valT_s cut into 2^sparse_gram_shift()-wide
 // blocks of batch positions, unpadded, as build_gram_blocked cuts the rows.
+// A multi-output context (scs_set_multi_sparse_batches): the columns are the data view's
+// (dc / dcp, not the variable count), the row side keeps the full copy's sub-block shift and kp, the
+// column side is cut at multi_spmm_shift(n_b, K) on the product-kernel arm (kp sub-blocks per partial)
+// and at spmv_blk_shift(n_b) on the loop arm, the K columns of Y are gathered and the workspace holds
+// one partial per (group, column).  Both copies carry the workgroup form of the one-pass kernel.
 // Returns the view's slot in spool / bplan.
 int build_sparse_view(scs_ctx* c, int64_t b, bool ssv) {
   const int64_t n = c->boff[b + 1] - c->boff[b], ng = c->bglob[b];
   const int64_t* rows = c->brows + c->boff[b];
-  const int64_t N = c->N, m = c->m;
+  const int64_t N = c->N, m = c->dc;   // (dc = the variable count unless nout is set)
+  const int64_t K = kout(c);
   const int f32 = c->sp_f32;
   const size_t vs = f32 ? sizeof(float) : sizeof(double);
   const SpBlkT& F = c->bcsr;
@@ -1135,8 +1152,11 @@ int build_sparse_view(scs_ctx* c, int64_t b, bool ssv) {
   SpBlkT &R = v.bcsr, &Cc = v.bcsc;   // owned by v from the start: free_view gives a failed build's arrays back
   R.shift = F.shift;
   R.nblk = F.nblk;
-  Cc.shift = spmv_blk_shift(n);
+  R.kp = F.kp;
+  Cc.kp = c->bcsc.kp;
+  Cc.shift = Cc.kp > 1 ? multi_spmm_shift(n, c->nout) : spmv_blk_shift(n);
   Cc.nblk = (int)std::max<int64_t>(ceil_div(n, int64_t(1) << Cc.shift), 1);
+  R.narrow = Cc.narrow = (multi(c) && F.kp > 1) ? c->msb_narrow : 0;
   const int64_t nkR = (int64_t)R.nblk * n, nkC = (int64_t)Cc.nblk * m;
   int64_t nnzpR = 0, nnzb = 0, nnzpC = 0;
   int64_t *ptrR = nullptr, *ptrC = nullptr, *colptr_b = nullptr, *bfirst = nullptr;
@@ -1222,8 +1242,10 @@ int build_sparse_view(scs_ctx* c, int64_t b, bool ssv) {
   auto ab = [](int64_t cnt, size_t eb) { return (int64_t)(std::max<int64_t>(cnt, 1) * (int64_t)eb); };
   const int64_t nR = n > 0 ? nkR + 1 : 1, nC = n > 0 ? nkC + 1 : 1;
   const int64_t nG = n > 0 ? nkG + 1 : 1;
-  const int64_t bytes = ab(v.Npad, 8) * 6 + ab((int64_t)R.nblk * v.Npad, 8) + ab(nval, 8) +
-                        ab((int64_t)Cc.nblk * c->mpad, 8) + ab(nR, 8) + ab(nC, 8) + ab(nnzpR + 8, 2) +
+  // (y, z, gN, hN: K columns each; wN, vN; zpart and tpart: one partial per (group, column))
+  const int64_t bytes = ab(v.Npad * K, 8) * 4 + ab(v.Npad, 8) * 2 + ab((int64_t)blk_groups(R) * v.Npad * K, 8) +
+                        ab(nval, 8) + ab((int64_t)blk_groups(Cc) * c->dcp * K, 8) + ab(nR, 8) + ab(nC, 8) +
+                        ab(nnzpR + 8, 2) +
                         ab(nnzpR + 8, vs) + ab(nnzpC + 8, 2) + ab(nnzpC + 8, vs) +
                         (ssv ? ab(n + 1, 8) + ab(nnzb, 4) + ab(nnzb, vs) + ab(nG, 8) + ab(nnzb + 8, 2) +
                                    ab(nnzb + 8, vs)
@@ -1253,8 +1275,9 @@ int build_sparse_view(scs_ctx* c, int64_t b, bool ssv) {
   Cc.lidx = dalloc<uint16_t>(c, nnzpC + 8, false);
   HCK(hipMemsetD16Async((hipDeviceptr_t)Cc.lidx, (unsigned short)pad, (size_t)(nnzpC + 8), c->st));
   Cc.val = f32 ? (void*)dalloc<float>(c, nnzpC + 8) : (void*)dalloc<double>(c, nnzpC + 8);
-  v.y = dalloc<double>(c, v.Npad, false);
-  HCK(launch_gather_y(c->y, rows, n, v.Npad, v.y, c->st));
+  v.y = dalloc<double>(c, v.Npad * K, false);
+  for (int64_t l = 0; l < K; ++l)   // Y_b: n_b x K with stride Npad_b
+    HCK(launch_gather_y(c->y + l * c->Npad, rows, n, v.Npad, v.y + l * v.Npad, c->st));
   if (n > 0) {
     HCK(hipMemcpyAsync(R.ptr, ptrR, sizeof(int64_t) * nR, hipMemcpyDeviceToDevice, c->st));
     HCK(hipMemcpyAsync(Cc.ptr, ptrC, sizeof(int64_t) * nC, hipMemcpyDeviceToDevice, c->st));
@@ -1305,15 +1328,15 @@ int build_sparse_view(scs_ctx* c, int64_t b, bool ssv) {
 // and re-gathered only when it holds another batch.  With scs_set_sparse_batches on, a sparse A
 // under ProxLQNSCORE gets the batch's sparse view instead: kept per batch within the budget, else
 // rebuilt into the refillable slot of its size (batch_plan.h).
-void select_batch(scs_ctx* c, int64_t b) {
+void select_batch(scs_ctx* c, int64_t b, bool dense_view = false) {   // dense_view: scs_get_batch_data's read
   unselect_view(c);
   c->bsel = b < 0 ? -1 : b;
   if (b < 0) return;
   // f(A, y, x) = 1/2 x'(A x) + y'x reads A as an m x m operator, not as samples
   if (c->loss == SCS_LOSS_QUADRATIC) fail(c, SCS_ERR_ARG, "the quadratic loss has no samples to batch");
   const int64_t n = c->boff[b + 1] - c->boff[b], ng = c->bglob[b];
-  const int kind = c->method_set ? batch_view_kind(c, c->method) : 0;
-  c->vkind = kind;
+  const int kind = (c->method_set && !dense_view) ? batch_view_kind(c, c->method) : 0;
+  if (!dense_view) c->vkind = kind;
   // (kind 2: a batch of the feature branch, n_b + 1 > m, keeps the dense view and the m x m Gram)
   if (kind == 1 || (kind == 2 && ng + 1 <= c->m)) {
     int ks = c->bplan.find(b);
@@ -1346,6 +1369,12 @@ void select_batch(scs_ctx* c, int64_t b) {
     if (n == 0) {
       HCK(hipMemsetAsync(v.A, 0, a_block_bytes(c, v.Npad, v.a32), c->st));
       HCK(hipMemsetAsync(v.y, 0, sizeof(double) * v.Npad * kout(c), c->st));
+    } else if (multi(c) && c->sparse) {   // scs_set_multi_sparse_batches: Matrix(As') of the d-column rows, Y_b
+      const int64_t* rows = c->brows + c->boff[b];
+      HCK(hipMemsetAsync(v.A, 0, a_block_bytes(c, v.Npad, 0), c->st));
+      HCK(launch_densify_rows(c->rowptr, c->colidx, c->val, c->sp_f32, rows, n, v.Npad, c->y, v.A, v.y, c->st));
+      for (int l = 1; l < c->nout; ++l)
+        HCK(launch_gather_y(c->y + (int64_t)l * c->Npad, rows, n, v.Npad, v.y + (int64_t)l * v.Npad, c->st));
     } else if (multi(c)) {   // scs_set_multi_batches (a dense A): dcp columns and the K target columns
       const int64_t* rows = c->brows + c->boff[b];
       if (c->mb_gather) {
@@ -1395,8 +1424,8 @@ int matvec_n(scs_ctx* c, const double* xd, int nsplit) {
     if (B.kp > 1) {   // one pass over the nonzeros for all K columns (multi_sparse.hip)
       HCK(launch_multi_spmm_pack(xd, c->dc, c->dc, c->dcp, K, c->mXt, c->st));
       HCK(launch_multi_spmm(B.ptr, B.lidx, B.val, c->sp_f32, c->mXt, K, c->N, c->dc, B.shift, c->zpart, c->Npad,
-                            c->st));
-      c->prod_kname = multi_spmm_kernel_name(c->sp_f32, K);
+                            c->st, B.narrow));
+      c->prod_kname = multi_spmm_kernel_name(c->sp_f32, K, B.narrow);
     } else {          // the loop arm: column l of vec(X) is contiguous at x + d*l
       for (int l = 0; l < K; ++l)
         HCK(launch_spmv_blk(B.ptr, B.lidx, B.val, c->sp_f32, xd + c->dc * l, c->N, c->dc, B.shift, c->nnz,
@@ -1457,7 +1486,8 @@ void matvec_t(scs_ctx* c, const double* v, double* out) {
     if (B.kp > 1) {
       double* Vt = multi_vt(c, c->Npad * B.kp);
       HCK(launch_multi_spmm_pack(v, c->Npad, c->Npad, c->Npad, K, Vt, c->st));
-      HCK(launch_multi_spmm(B.ptr, B.lidx, B.val, c->sp_f32, Vt, K, c->dc, c->N, B.shift, c->tpart, c->dcp, c->st));
+      HCK(launch_multi_spmm(B.ptr, B.lidx, B.val, c->sp_f32, Vt, K, c->dc, c->N, B.shift, c->tpart, c->dcp, c->st,
+                            B.narrow));
     } else {
       for (int l = 0; l < K; ++l)
         HCK(launch_spmv_blk(B.ptr, B.lidx, B.val, c->sp_f32, v + (int64_t)l * c->Npad, c->dc, c->N, B.shift, c->nnz,
@@ -3452,6 +3482,15 @@ static int multi_gather_arm(int a32) {
   return multi_gather_default(a32);
 }
 
+// The workgroup form of the one-pass K-column kernel on sparse batch views (scs_set_multi_sparse_batches):
+// 1 the 256-row form, 0 the 1024-row form.  Both write the same bits.  SCS_MULTI_SPARSE_NARROW=0 / 1
+// forces a form (read where the list is registered); the default is multi_spmm_narrow_default in
+// multi_sparse.hip, the one place of the rule.
+static int multi_narrow_form(int K, int f32) {
+  if (const char* e = std::getenv("SCS_MULTI_SPARSE_NARROW")) return e[0] != '0';
+  return multi_spmm_narrow_default(K, f32);
+}
+
 static void set_dims(scs_ctx* c, int64_t N, int64_t m, int64_t Nglob, int64_t row0) {
   if (m <= 0 || N < 0) fail(c, SCS_ERR_ARG, "bad dimensions N=%lld m=%lld", (long long)N, (long long)m);
   c->N = N;
@@ -3811,10 +3850,18 @@ int scs_batch_info(scs_ctx* c, int64_t* nviews, int64_t* view_bytes, int64_t* bu
     return SCS_OK;
   }
   return guarded(c, [&] {
-    int64_t nv = 0;
+    int64_t nv = 0, vb = c->bplan.total_bytes();
     for (const scs::BatchSlot& s_ : c->bplan.slots) nv += s_.batch >= 0 ? 1 : 0;
+    if (multi(c) && c->sparse)   // scs_set_multi_sparse_batches: the densified pool views count too
+      for (size_t i = 0; i < c->bpool.size(); ++i) {
+        if (c->bheld[i] < 0) continue;
+        ++nv;
+        size_t t = 0;
+        view_buffers(c->bpool[i], VB_ALL, [&](const void* q) { t += alloc_bytes(c, q); });
+        vb += (int64_t)t;
+      }
     if (nviews) *nviews = nv;
-    if (view_bytes) *view_bytes = c->bplan.total_bytes();
+    if (view_bytes) *view_bytes = vb;
     if (builds) *builds = c->bplan.builds;
   });
 }
@@ -4834,11 +4881,13 @@ int scs_set_batches(scs_ctx* c, const int64_t* rows, const int64_t* offsets, int
       fail(c, SCS_ERR_ARG, "scs_set_batches: minibatches (batch_size / slice_samples) are not supported with "
                            "scs_set_outputs (nout = %d) unless multi_batches / scs_set_multi_batches is on", c->nout);
     if (!c->has_data) fail(c, SCS_ERR_STATE, "no data: call scs_set_data / scs_gen_data first");
-    if (multi(c) && c->sparse)
+    if (multi(c) && c->sparse && !c->multi_sparse_batches)
       fail(c, SCS_ERR_ARG, "scs_set_batches: minibatches with scs_set_outputs (nout = %d) need a dense A (a sparse A, "
                            "scs_set_sparse_outputs included, is not supported with multi_batches / "
-                           "scs_set_multi_batches)", c->nout);
-    if (multi(c)) c->mb_gather = multi_gather_arm(c->a32);
+                           "scs_set_multi_batches) unless multi_sparse_batches / scs_set_multi_sparse_batches is on",
+           c->nout);
+    if (multi(c) && !c->sparse) c->mb_gather = multi_gather_arm(c->a32);
+    if (multi(c) && c->sparse) c->msb_narrow = multi_narrow_form(c->nout, c->sp_f32);
     if (c->generic) fail(c, SCS_ERR_ARG, "a ProblemGeneric has no samples to batch");
     if (nbatch < 0 || !rows || !offsets || offsets[0] != 0) fail(c, SCS_ERR_ARG, "scs_set_batches: bad batch list");
     for (int64_t b = 0; b < nbatch; ++b)
@@ -5859,7 +5908,7 @@ int scs_set_multi_sample(scs_ctx* c, int on) {
     const int v = on ? 1 : 0;
     if (v == c->multi_sample) return;
     c->multi_sample = v;
-    if (!v && multi(c) && c->has_data && !c->sparse) {   // the view in place and every pooled batch view
+    if (!v && multi(c) && c->has_data) {   // the view in place (a dense A) and every pooled batch view
       HCK(hipSetDevice(c->dev));
       sync(c);
       auto give_back = [c](ViewData& w) {
@@ -5867,7 +5916,7 @@ int scs_set_multi_sample(scs_ctx* c, int on) {
         free_buffers(c, w, VB_SAMPLE);
         static_cast<ViewSample&>(w) = ViewSample();
       };
-      give_back(*c);
+      if (!c->sparse) give_back(*c);
       for (NView& w : c->bpool) give_back(w);
     }
   });
@@ -5889,6 +5938,35 @@ int scs_set_multi_batches(scs_ctx* c, int on) {
     sync(c);
     c->multi_batches = v;
     if (!v && multi(c) && !c->boff.empty()) {
+      clear_batches(c);
+    } else {
+      free_dense_views(c);   // the pooled views go, the registered list stays
+      free_sparse_views(c);
+      if (c->bsel >= 0) select_batch(c, c->bsel);
+    }
+    invalidate_caches(c);
+    sync(c);
+  });
+}
+
+// Minibatches with nout set on a sparse A (scs_set_sparse_outputs): lifts scs_set_batches' dense-A
+// requirement; scs_set_multi_batches stays the gate.  Stored without effect while nout is unset or on a
+// dense A.  Changing it drops the pooled batch views; switching it off with a list registered on a sparse
+// multi-output context clears the list.
+int scs_set_multi_sparse_batches(scs_ctx* c, int on) {
+  if (!c) return SCS_ERR_ARG;
+  if (is_group(c)) {
+    c->err = "scs_set_multi_sparse_batches takes a single-device context (scs_create): a multi-device context "
+             "(devices=[...]) is not supported with nout";
+    return SCS_ERR_ARG;
+  }
+  return guarded(c, [&] {
+    const int v = on ? 1 : 0;
+    if (v == c->multi_sparse_batches) return;
+    HCK(hipSetDevice(c->dev));
+    sync(c);
+    c->multi_sparse_batches = v;
+    if (!v && multi(c) && c->sparse && !c->boff.empty()) {
       clear_batches(c);
     } else {
       free_dense_views(c);   // the pooled views go, the registered list stays
@@ -5928,10 +6006,28 @@ int scs_get_batch_data(scs_ctx* c, int64_t b, double* A_out, int64_t lda, double
         }
       }
     } restore{c, was};
-    select_batch(c, b);
+    // a sparse multi-output context (scs_set_multi_sparse_batches): the batch's densified view whatever
+    // kind the method asks for; a pool view made for this read alone goes with it
+    const bool msb = multi(c) && c->sparse;
+    const size_t npool = c->bpool.size();
+    struct DropView {
+      scs_ctx* c;
+      size_t npool;
+      ~DropView() {
+        if (c->bpool.size() <= npool) return;
+        (void)hipStreamSynchronize(c->st);
+        free_view(c, c->bpool.back());
+        c->bpool.pop_back();
+        c->bheld.pop_back();
+        c->bview = -1;
+      }
+    } drop{c, msb ? npool : (size_t)-1};
+    select_batch(c, b, msb);
     if (c->spview >= 0) fail(c, SCS_ERR_ARG, "scs_get_batch_data: batch %lld is held as a sparse view", (long long)b);
-    BatchScope bs(c);
-    read_rows(c, 0, c->N, A_out, lda, Y_out);
+    {
+      BatchScope bs(c);
+      read_rows(c, 0, c->N, A_out, lda, Y_out);
+    }
   });
 }
 
@@ -5945,6 +6041,9 @@ int scs_multi_products_eval(scs_ctx* c, int K, const double* X, const double* V,
     if ((X == nullptr) != (AX == nullptr) || (V == nullptr) != (ATV == nullptr))
       fail(c, SCS_ERR_ARG, "scs_multi_products_eval: X goes with AX and V with ATV");
     HCK(hipSetDevice(c->dev));
+    // a selected sparse batch view (scs_set_multi_sparse_batches) takes the data's place: V is n_b x K
+    std::unique_ptr<BatchScope> bs;
+    if (multi(c) && c->spview >= 0) bs.reset(new BatchScope(c));
     const int64_t N = c->N, Npad = c->Npad, d = c->dc, dcp = c->dcp;
     if (c->sparse) {   // the step's own matvec_n / matvec_t on the context's workspace
       if (K != c->nout)

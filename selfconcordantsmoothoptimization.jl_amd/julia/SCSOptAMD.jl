@@ -17,6 +17,7 @@ import SelfConcordantSmoothOptimization: step!, init!, ProximalMethod, ProxModel
 export DeviceProblem, configure!, iterate_device!, set_gram_cache!, set_solver!, rccl_unique_id, set_comm_rccl!,
        set_comm_callback!, set_test!, set_test_device!, set_compute_f32!, fallback_counts, data_info, samplewise,
        set_sparse_batches!, set_sparse_sample!, batch_info, set_multi_sample!, set_multi_batches!,
+       set_multi_sparse_batches!,
        multi_sample_system
 
 const lib = joinpath(@__DIR__, "..", "scsopt", "libscsopt.so")
@@ -325,6 +326,14 @@ function set_multi_batches!(model::DeviceProblem, on::Bool=true)
     return model
 end
 
+# Minibatches of a multi-output problem on a sparse A on or off (scs_set_multi_sparse_batches; off by
+# default: set_batches! asks for a dense A).  set_multi_batches! stays the gate.  Stored without effect
+# without nout or on a dense A; switching it off clears a sparse multi-output problem's registered list.
+function set_multi_sparse_batches!(model::DeviceProblem, on::Bool=true)
+    chk(ccall((:scs_set_multi_sparse_batches, lib), Cint, (Ptr{Cvoid}, Cint), model.ctx, on ? 1 : 0), model.ctx)
+    return model
+end
+
 # (M, b) of the sample-space system a multi-output ProxGGNSCORE step solves at x (multi_sample = true;
 # the regularizer and the smoother set): M of order N*K + 1, rows and columns (i, k) = i + N*k
 function multi_sample_system(model::DeviceProblem, x::Vector{Float64})
@@ -473,16 +482,26 @@ end
 # X0 d x K, loss :softmax_ce / :multi_least_squares as for the dense method above.  With
 # sparse_outputs = true the sparse doors accept A under scs_set_outputs and the products A*X, A'*R read
 # the nonzeros once for all K columns; without it the library refuses, naming the switch.  One device,
-# one rank, the full batch; a sparse Atest takes an Ntest x K ytest.
+# one rank; a sparse Atest takes an Ntest x K ytest.  Minibatches need multi_batches = true (the gate,
+# scs_set_multi_batches) and multi_sparse_batches = true (scs_set_multi_sparse_batches, which lifts the
+# dense-A requirement): a batch is then a densified view or, with sparse_batches = true under ProxLQNSCORE,
+# a sparse K-column view.
 function DeviceProblem(A::SparseMatrixCSC{Float64}, Y::AbstractMatrix, x0::Vector{Float64}, loss::Symbol, λ;
                        sparse_outputs::Bool=false, out_fn::Union{Symbol,Nothing}=nothing,
                        scale::Float64=1.0 / size(A, 1), L=nothing, sol::Vector{Float64}=zero(x0), C_set=nothing,
-                       P=nothing, device::Integer=0, val_f32::Bool=false, Atest=nothing, ytest=nothing)
+                       P=nothing, device::Integer=0, val_f32::Bool=false, Atest=nothing, ytest=nothing,
+                       multi_sample::Bool=false, multi_batches::Bool=false, sparse_batches::Bool=false,
+                       multi_sparse_batches::Bool=false)
     N, d = size(A)
     K = size(Y, 2)
     (size(Y, 1) == N && length(x0) == d * K) ||
         throw(DimensionMismatch("Y must be N x K and length(x0) = size(A, 2) * K"))
     ctx = create_ctx(device)
+    multi_sample && chk(ccall((:scs_set_multi_sample, lib), Cint, (Ptr{Cvoid}, Cint), ctx, 1), ctx)
+    multi_batches && chk(ccall((:scs_set_multi_batches, lib), Cint, (Ptr{Cvoid}, Cint), ctx, 1), ctx)
+    sparse_batches && chk(ccall((:scs_set_sparse_batches, lib), Cint, (Ptr{Cvoid}, Cint), ctx, 1), ctx)
+    multi_sparse_batches &&
+        chk(ccall((:scs_set_multi_sparse_batches, lib), Cint, (Ptr{Cvoid}, Cint), ctx, 1), ctx)
     chk(ccall((:scs_set_sparse_outputs, lib), Cint, (Ptr{Cvoid}, Cint), ctx, sparse_outputs ? 1 : 0), ctx)
     chk(ccall((:scs_set_outputs, lib), Cint, (Ptr{Cvoid}, Cint), ctx, K), ctx)
     Ym = Matrix{Float64}(Y)

@@ -117,6 +117,7 @@ _SIGS = {
     "scs_set_sparse_outputs": (C.c_int, [C.c_void_p, C.c_int]),
     "scs_set_multi_sample": (C.c_int, [C.c_void_p, C.c_int]),
     "scs_set_multi_batches": (C.c_int, [C.c_void_p, C.c_int]),
+    "scs_set_multi_sparse_batches": (C.c_int, [C.c_void_p, C.c_int]),
     "scs_get_outputs": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), c_i64p]),
     "scs_set_data": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, c_dp, C.c_int64, c_dp, C.c_int64, C.c_int64]),
     "scs_gen_data": (C.c_int, [C.c_void_p, C.POINTER(Synth)]),

@@ -90,6 +90,7 @@ def init_method(method, model):
     mem = method.m if isinstance(method, ProxLQNSCORE) else 0
     model.ctx.check(_lib.lib.scs_method_init(model.ctx.h, method.code, int(method.ss_type), int(bool(method.use_prox)),
                                              int(mem)))
+    model._method_code = method.code   # (Problem.multi_products: which view a selected batch is held as)
 
 
 def loader_batches(N, batch_size=None, slice_samples=False, shuffle_batch=True, local_max_iter=None, perm=None,

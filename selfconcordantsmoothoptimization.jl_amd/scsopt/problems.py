@@ -97,7 +97,7 @@ class Problem:
                  out_fn: Optional[OutFn] = None, name=None, device=0, comm=None, N_global=None, row0=0,
                  sparse_f32=False, devices=None, device_exchange="rccl", Ntest_global=None, test_row0=0,
                  dense_f32=False, sparse_batches=False, sparse_sample=False, sparse_outputs=False, multi_sample=False,
-                 multi_batches=False, _ctx=None):
+                 multi_batches=False, multi_sparse_batches=False, _ctx=None):
         if len(args) == 5:
             A, y, x0, f, lam = args
         elif len(args) == 3:
@@ -140,6 +140,17 @@ class Problem:
         if self.multi_batches and devices is not None:
             raise ValueError("multi_batches=True takes a single-device context: devices=[...] is not supported with "
                              "nout")
+        # multi_sparse_batches: with nout and multi_batches set, minibatches of a sparse A (sparse_outputs) are
+        # accepted as well: densified views, or sparse K-column views under ProxLQNSCORE with sparse_batches
+        # (scs_set_multi_sparse_batches)
+        if not isinstance(multi_sparse_batches, (bool, np.bool_)):
+            raise TypeError(f"multi_sparse_batches must be a bool, got {type(multi_sparse_batches).__name__}")
+        self.multi_sparse_batches = bool(multi_sparse_batches)
+        if self.multi_sparse_batches and devices is not None:
+            raise ValueError("multi_sparse_batches=True takes a single-device context: devices=[...] is not supported "
+                             "with nout")
+        self._sparse_batches = bool(sparse_batches)
+        self._sparse_A = _lib.is_device_csr(A) or _is_sparse(A)
         self.nout = self._check_outputs(f, out_fn, A, comm, devices, _ctx)
         self.d = self.m // self.nout   # A's columns
         if f.kind == "callback":   # the data stays with the caller's closures; the device holds none
@@ -170,6 +181,8 @@ class Problem:
             self.ctx.check(_lib.lib.scs_set_multi_sample(self.ctx.h, 1))
         if self.multi_batches:    # likewise
             self.ctx.check(_lib.lib.scs_set_multi_batches(self.ctx.h, 1))
+        if self.multi_sparse_batches:   # likewise, and inert on a dense A
+            self.ctx.check(_lib.lib.scs_set_multi_sparse_batches(self.ctx.h, 1))
         if self.nout > 1:   # before the data door: its m is then A's column count d, y is N x nout
             self.ctx.check(_lib.lib.scs_set_outputs(self.ctx.h, self.nout))
         if comm is not None and comm.active and _ctx is None:
@@ -860,6 +873,7 @@ class Problem:
         SCS_SPARSE_BATCH_CACHE_MB).  ProxNSCORE / ProxGGNSCORE keep the dense view.  Changing the mode
         drops the pooled views; the registered list stays.  scs_set_sparse_batches."""
         self.ctx.check(_lib.lib.scs_set_sparse_batches(self.ctx.h, int(bool(on))))
+        self._sparse_batches = bool(on)
 
     def set_sparse_sample(self, on=True):
         """Opt-in: ProxGGNSCORE's sample-space branch (N + 1 <= m) on a sparse A forms P = A diag(1/Hr) Aᵀ
@@ -887,6 +901,27 @@ class Problem:
         self.multi_batches = bool(on)
         if not self.multi_batches and self.nout > 1:
             self._bsel, self._bsizes = -1, []
+
+    def set_multi_sparse_batches(self, on=True):
+        """Opt-in: with nout and multi_batches set, set_batches / iterate(batch_size=..., slice_samples=...) also
+        accept a sparse A held with sparse_outputs.  A batch is a densified view (its CSR rows written into a dense
+        n_b x d block, Y_b gathered; all three methods, ProxGGNSCORE picking its branch per batch) or, with
+        sparse_batches also on and ProxLQNSCORE, a sparse K-column view.  Off: the dense-A refusal.  Stored without
+        effect while nout is unset or on a dense A; changing it drops the pooled views, and switching it off
+        clears a sparse multi-output problem's registered list.  scs_set_multi_sparse_batches."""
+        self.ctx.check(_lib.lib.scs_set_multi_sparse_batches(self.ctx.h, int(bool(on))))
+        self.multi_sparse_batches = bool(on)
+        if not self.multi_sparse_batches and self.nout > 1 and self._sparse_A:
+            self._bsel, self._bsizes = -1, []
+
+    def _products_rows(self):
+        """The rows multi_products runs on: the selected batch's on a sparse K-column view (a sparse multi-output
+        problem with multi_sparse_batches and sparse_batches under ProxLQNSCORE), else the full data's."""
+        sel = getattr(self, "_bsel", -1)
+        if (sel >= 0 and self.nout > 1 and self._sparse_A and self.multi_sparse_batches and self._sparse_batches
+                and getattr(self, "_method_code", None) == 3):   # ProxLQNSCORE.code
+            return self._bsizes[sel]
+        return self.N
 
     def get_batch_data(self, b):
         """(A_b, y_b) of registered batch b as a step sees it, gathered by select_batch's own path: the n_b x d
@@ -973,21 +1008,28 @@ class Problem:
     def multi_products(self, X=None, V=None):
         """A X (N x K) and Aᵀ V (d x K) through the multi-output kernels (scs_multi_products_eval); X is
         d x K, V is N x K, 1 <= K <= 16 (K need not be the problem's nout).  Returns (AX, ATV), None for
-        an operand not given."""
+        an operand not given.  With a sparse batch view selected (multi_sparse_batches) the products run on that
+        view: N is then the batch's n_b."""
         K = (X if X is not None else V).shape[1]
+        N = self._products_rows()
+        cap = max(N, self.N) * K   # the buffers hold the full data's rows whatever view the context selects
         ax = atv = Xf = Vf = None
         if X is not None:
             Xf = np.asfortranarray(np.asarray(X, dtype=np.float64))
             if Xf.shape != (self.d, K):
                 raise ValueError(f"X must be d x K = ({self.d}, {K})")
-            ax = np.zeros((self.N, K), order="F")
+            ax = np.zeros(cap)
         if V is not None:
-            Vf = np.asfortranarray(np.asarray(V, dtype=np.float64))
-            if Vf.shape != (self.N, K):
-                raise ValueError(f"V must be N x K = ({self.N}, {K})")
+            V = np.asarray(V, dtype=np.float64)
+            if V.shape != (N, K):
+                raise ValueError(f"V must be N x K = ({N}, {K})")
+            Vf = np.zeros(cap)
+            Vf[:N * K] = V.reshape(-1, order="F")
             atv = np.zeros((self.d, K), order="F")
         p = lambda a: None if a is None else C.cast(a.ctypes.data, _lib.c_dp)   # noqa: E731
         self.ctx.check(_lib.lib.scs_multi_products_eval(self.ctx.h, int(K), p(Xf), p(Vf), p(ax), p(atv)))
+        if ax is not None:
+            ax = ax[:N * K].reshape((N, K), order="F")
         return ax, atv
 
     def multi_system(self, x):
