@@ -673,6 +673,19 @@ int scs_gram_eval(scs_ctx* ctx, const double* w, double* G, int64_t ldg);
  * ProxGGNSCORE sample-space step forms it (from the nonzeros with scs_set_sparse_sample on a sparse
  * A, else Aᵀ copy + tiles), symmetrized; N x N into P, ldp >= N.  One rank.                     */
 int scs_sample_gram_eval(scs_ctx* ctx, const double* h, double* P, int64_t ldp);
+/* The sample-space system of a single-output ProxGGNSCORE step at x (prox-GGN-SCORE.jl:124-127), of
+ * the selected batch or the full data, before the solve: x is uploaded, the smoother evaluated, then
+ * the function the step itself calls runs the forward pass, P = A diag(1 ./ Hr) A', u = A (h .* lambda gr)
+ * and the assembly -- on the context's own arm (a dense A, fp64 or fp32-stored; a sparse A from its
+ * nonzeros with scs_set_sparse_sample, else from its dense mirror) and its cached A' copy, tile list
+ * and scratch.  M of order n1 = N + 1 (column-major, ldm >= n1; nothing is written beyond order n1):
+ * M[i][j] = delta_ij + q_i s_i s_j P_ij, M[i][N] = q_i s_i u_i, M[N][.] = e_N; b = [r; 1] (n1).  M or b
+ * may be NULL.  SCS_ERR_STATE without data, loss, regularizer or smoother, on a multi-output context
+ * (scs_multi_sample_system_eval serves it), or while the selected batch is held as ProxLQNSCORE's
+ * sparse view (scs_set_sparse_batches: it keeps no rows for this system); SCS_ERR_ARG when N + 1 > m (the feature branch's shape:
+ * scs_solve_eval / scs_gram_eval), without a GGN kind, on a callback loss (its J is the caller's), on
+ * more than one rank, for a NULL x or ldm < n1.  A refusal leaves the context usable.               */
+int scs_sample_system_eval(scs_ctx* ctx, const double* x, double* M, int64_t ldm, double* b);
 /* out = Aᵀ v (local rows)                                                  */
 int scs_gemv_t_eval(scs_ctx* ctx, const double* v, double* out);
 /* out = A x (local rows)                                                   */

@@ -2761,9 +2761,10 @@ void sample_space_solve(scs_ctx* c, double* Ms, int64_t np1, int64_t n1, double*
   tend(c, T_SOLVE, e0);
 }
 
-void ggn_sample_direction(scs_ctx* c, const double* xh) {
+// The system of the branch at x (c->x, smoother evaluated): the forward pass, P = A diag(h) Aᵀ, u and the
+// assembly into S.Ms / S.bS (row-major, order N + 1, padded order S.n1pad) -- everything before the solve
+const SampleSys& ggn_sample_system(scs_ctx* c, const double* xh) {
   const int64_t N = c->N, m = c->m;
-  if (sharded(c)) return ggn_sample_direction_sharded(c, xh);
   const bool sps = sparse_sample_path(c);
   if (!sps && c->At && c->loss == SCS_LOSS_CALLBACK)   // the caller's J changes every step
     HCK(launch_transpose(c->A, c->a32, c->Npad, N, m, c->At, c->mpad, c->ss.NpS, c->st));
@@ -2809,13 +2810,20 @@ void ggn_sample_direction(scs_ctx* c, const double* xh) {
                       uN, nullptr, nullptr, nullptr, nullptr, c->valpart, c->st));
   HCK(launch_ggn_sample_assemble(Ps, NpS, c->gN, c->hN, c->wN, uN, nullptr, N, Ms, n1pad, bS,
                                       c->st));
-  sample_space_solve(c, Ms, n1pad, N + 1, bS, [&] {   // the system assembled again
-    HCK(launch_ggn_sample_assemble(Ps, NpS, c->gN, c->hN, c->wN, uN, nullptr, N, Ms, n1pad, bS,
+  return S;
+}
+
+void ggn_sample_direction(scs_ctx* c, const double* xh) {
+  const int64_t N = c->N, m = c->m;
+  if (sharded(c)) return ggn_sample_direction_sharded(c, xh);
+  const SampleSys& S = ggn_sample_system(c, xh);
+  sample_space_solve(c, S.Ms, S.n1pad, N + 1, S.bS, [&] {   // the system assembled again
+    HCK(launch_ggn_sample_assemble(S.Ps, S.NpS, c->gN, c->hN, c->wN, S.uN, nullptr, N, S.Ms, S.n1pad, S.bS,
                                    c->st));
   });
-  HCK(launch_ggn_sample_scale(c->gN, bS, N, c->Npad, c->vN, c->st));
+  HCK(launch_ggn_sample_scale(c->gN, S.bS, N, c->Npad, c->vN, c->st));
   gemv_t_local(c, c->vN, c->gtmp);   // Aᵀ(s∘B)
-  HCK(launch_ggn_sample_direction(hvec, c->gtmp, hg, bS, N, m, c->d, c->st));
+  HCK(launch_ggn_sample_direction(S.hvec, c->gtmp, S.hg, S.bS, N, m, c->d, c->st));
 }
 
 // host column-major rows (N x m, lda) -> panel-blocked dst (Npad x mpad), one 128-column panel
@@ -5591,6 +5599,63 @@ int scs_sample_gram_eval(scs_ctx* c, const double* h, double* P, int64_t ldp) {
       HCK(hipMemcpy2DAsync(P, sizeof(double) * ldp, Ps, sizeof(double) * NpS, sizeof(double) * N, N,
                            hipMemcpyDeviceToHost, c->st));
     sync(c);
+    if (c->timing) tresolve(c);
+  });
+}
+
+// the sample-space system of a single-output ProxGGNSCORE step at x, of the selected batch or the full
+// data: the smoother, then the function the step calls (ggn_sample_system: its cached Aᵀ / tile list /
+// scratch, or P from the nonzeros), before the solve.  M of order n1 = N + 1 and b
+int scs_sample_system_eval(scs_ctx* c, const double* x, double* M, int64_t ldm, double* b) {
+  return guarded(c, [&] {
+    if (multi(c))
+      fail(c, SCS_ERR_STATE, "scs_sample_system_eval takes a single-output context: this one has nout = %d "
+                             "(scs_multi_sample_system_eval serves it)", c->nout);
+    if (!c->loss_set) fail(c, SCS_ERR_STATE, "no loss: call scs_set_loss first");
+    if (c->loss == SCS_LOSS_CALLBACK)
+      fail(c, SCS_ERR_ARG, "scs_sample_system_eval: a callback loss brings its own J (the system of the caller's "
+                           "rows is not the data's)");
+    if (!c->has_data || c->generic) fail(c, SCS_ERR_STATE, "no data");
+    if (!c->reg_set || !c->smooth_set)
+      fail(c, SCS_ERR_STATE, "scs_sample_system_eval needs the regularizer and the smoother (h = 1 ./ Hr, λ gr)");
+    if (sharded(c)) fail(c, SCS_ERR_ARG, "scs_sample_system_eval runs on one rank");
+    if (c->ggn == SCS_GGN_NONE) fail(c, SCS_ERR_ARG, "scs_sample_system_eval needs an out_fn / GGN loss kind");
+    HCK(hipSetDevice(c->dev));
+    BatchScope scope(c);
+    const int64_t N = c->N, n1 = N + 1;
+    // (a sparse view built for ProxLQNSCORE's products holds neither the CSR rows nor a sample-space copy)
+    if (c->spview >= 0 && !sparse_sample_path(c))
+      fail(c, SCS_ERR_STATE, "scs_sample_system_eval: the selected batch is held as a sparse view of ProxLQNSCORE's "
+                             "products (scs_set_sparse_batches), which keeps no rows for the sample-space system");
+    if (c->Nglob + 1 > c->m)
+      fail(c, SCS_ERR_ARG, "scs_sample_system_eval: N + 1 = %lld > m = %lld is the feature branch's shape "
+                           "(scs_solve_eval / scs_gram_eval serve it)", (long long)(c->Nglob + 1), (long long)c->m);
+    if (!x) fail(c, SCS_ERR_ARG, "scs_sample_system_eval: null x");
+    if (M && ldm < n1)
+      fail(c, SCS_ERR_ARG, "scs_sample_system_eval: ldm %lld < N + 1 = %lld", (long long)ldm, (long long)n1);
+    invalidate_caches(c);
+    h2d(c, c->x, x, c->m);
+    HCK(launch_smoother(c->smooth, c->x, c->m, c->mu, c->slb, c->sub, c->wel, c->gr, c->Hr, c->st));
+    const SampleSys& S = ggn_sample_system(c, x);
+    // Ms is row-major: its transpose lands column-major on the host through a column-major staging copy
+    if (M) {
+      double* T = dalloc<double>(c, (size_t)S.n1pad * S.n1pad, false);
+      struct Free {
+        scs_ctx* c;
+        double** p;
+        ~Free() {
+          (void)hipStreamSynchronize(c->st);
+          dfree_t(c, *p);
+        }
+      } fr{c, &T};
+      HCK(qr_from_rowmajor(S.Ms, S.n1pad, T, S.n1pad, n1, S.n1pad, c->st));
+      HCK(hipMemcpy2DAsync(M, sizeof(double) * ldm, T, sizeof(double) * S.n1pad, sizeof(double) * n1, n1,
+                           hipMemcpyDeviceToHost, c->st));
+      sync(c);
+    }
+    if (b) d2h(c, b, S.bS, n1);
+    sync(c);
+    invalidate_caches(c);
     if (c->timing) tresolve(c);
   });
 }

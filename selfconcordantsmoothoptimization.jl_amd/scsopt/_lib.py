@@ -182,6 +182,7 @@ _SIGS = {
     "scs_prox_eval": (C.c_int, [C.c_void_p, c_dp, c_dp, C.c_double, C.c_double, c_dp]),
     "scs_gram_eval": (C.c_int, [C.c_void_p, c_dp, c_dp, C.c_int64]),
     "scs_sample_gram_eval": (C.c_int, [C.c_void_p, c_dp, c_dp, C.c_int64]),
+    "scs_sample_system_eval": (C.c_int, [C.c_void_p, c_dp, c_dp, C.c_int64, c_dp]),
     "scs_gemv_t_eval": (C.c_int, [C.c_void_p, c_dp, c_dp]),
     "scs_gemv_n_eval": (C.c_int, [C.c_void_p, c_dp, c_dp]),
     "scs_solve_eval": (C.c_int, [C.c_void_p, c_dp, c_dp, c_dp, C.c_int, c_dp, C.POINTER(C.c_int)]),

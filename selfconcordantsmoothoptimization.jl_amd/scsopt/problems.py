@@ -981,6 +981,21 @@ class Problem:
         self.ctx.check(_lib.lib.scs_sample_gram_eval(self.ctx.h, dptr(h), dptr(P), n))
         return P
 
+    def sample_system(self, x):
+        """(M, b) of the sample-space system a single-output ProxGGNSCORE step solves at x (N + 1 <= m, a GGN
+        loss kind; configure() first: h = 1 ./ Hr and λ gr enter it), of the selected batch or the full data, by
+        the step's own function up to the solve (scs_sample_system_eval).  M has order N + 1, column-major."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.shape != (self.m,):
+            raise ValueError(f"x must have length m = {self.m}")
+        sel = getattr(self, "_bsel", -1)
+        n1 = (self.N if sel < 0 else self._bsizes[sel]) + 1   # the rows select_batch chose last
+        Mm = np.zeros((n1, n1), order="F")
+        b = np.empty(n1)
+        self.ctx.check(_lib.lib.scs_sample_system_eval(self.ctx.h, dptr(x), C.cast(Mm.ctypes.data, _lib.c_dp), n1,
+                                                       dptr(b)))
+        return Mm, b
+
     def gemv_t(self, v):
         v = np.ascontiguousarray(v, dtype=np.float64)
         out = np.empty(self.m)
